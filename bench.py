@@ -1,10 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json metric: Mqueries/s of batched k-step FM-index
 backward search (3 Gbase synthetic reference, 10M x 100 bp reads, K=2, d=64)
-on N MI355X, one process per GPU, plus the achieved HBM fraction of the LF
-kernel and the CPU oracle timed on the host cores.
+on N MI355X, one process per GPU.  A plain run sets up, warms up, times the
+steps and prints its line; with --full it goes on to the achieved HBM fraction
+of the LF kernel, the md5 pins and oracle sample, the other configs and
+backends and the CPU oracle timed on the host cores.
 
   python bench.py --gpus 1 --steps 10 --warmup 20
+  python bench.py --gpus 1 --steps 10 --warmup 20 --full
+  python bench.py --gpus 1 --steps 10 --warmup 20 --dump-outputs DIR
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N
 
@@ -16,6 +20,7 @@ reads (weak scaling).  Rank 0 prints one JSON line.
 from __future__ import annotations
 
 import argparse
+import ctypes
 import hashlib
 import json
 import os
@@ -79,7 +84,7 @@ def log(*a, brief: bool = False):
         print(line if verbose else line[:160], file=sys.stderr, flush=True)
 
 
-def parse():
+def parse(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=10)
@@ -122,9 +127,29 @@ def parse():
     p.add_argument("--no-config1", dest="config1", action="store_false",
                    help="skip the 64 Mbase / 2^20-read leg (BASELINE config #1)")
     p.add_argument("--detail", default=None,
-                   help="where the full record goes (default gpurun_out/bench_detail_n<N>.json, else TMPDIR); "
-                        "the JSON line carries its path")
-    return p.parse_args()
+                   help="where the full record goes (with --full: default bench_detail_n<N>.json in the tree's "
+                        "output folder, else TMPDIR); the JSON line carries its path")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run every other leg: md5 pins and oracle parity sample, roofline "
+                        "(distinct blocks, replay and gather probes), config #5, ingest, K = 4 / 3 / derived, locate, "
+                        "the other backends, group replication, end to end, CPU baselines, config #1; the options "
+                        "that size or skip those legs apply only with it")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps write what the last timed step computed (rank 0's [L, R) interval "
+                        "per read, a fixed seeded sample of the reads when they are many) as DIR/<name>.npy")
+    a = p.parse_args(argv)
+    if not a.full:
+        plain_run(a)
+    return a
+
+
+def plain_run(a) -> None:
+    """Without --full the run is set-up, warm-up, the timed steps and the line:
+    every leg with a switch of its own is switched off here, the others ask
+    a.full where they start."""
+    a.no_md5, a.parity_sample, a.cpu_sample, a.config1 = True, 0, 0, False
+    a.config5_queries, a.ingest, a.kstep4 = 0, "off", False
+    a.variants, a.e2e_steps = "", 0
 
 
 def _free_port() -> int:
@@ -347,12 +372,14 @@ def aggregate_devices(rows: list) -> dict:
 
 
 def cuda_sync(dev: int):
-    try:
-        import torch
-        if torch.cuda.is_available():
-            torch.cuda.synchronize(dev)
-    except Exception:
-        pass
+    """Everything queued on device `dev` is done: hipDeviceSynchronize of the
+    HIP runtime the library is linked with (every stream, the library's own
+    non-blocking one included).  Straight through the runtime's C ABI, so a
+    one-GPU run need not import torch for it (3.5 s of its set-up, 11 s in the
+    first process on a machine); at N > 1 torch is the gloo control plane."""
+    hip = K.load()
+    if hip.hipSetDevice(ctypes.c_int(dev)) or hip.hipDeviceSynchronize():
+        raise RuntimeError(f"bench.py: hipDeviceSynchronize on device {dev} failed")
 
 
 def bench_text(D, n: int):
@@ -374,6 +401,48 @@ def bench_text(D, n: int):
         buf[off:off + len(ch)] = ch
         off += len(ch)
     return buf
+
+
+def read_starts(n_text: int, num: int, m: int, seed: int) -> np.ndarray:
+    """synth.read_starts' numbers -- random.Random(seed).randint(0, n_text - m),
+    num times -- without a Python call per read (10M of them are seconds of
+    every run's set-up).  randint draws k = bit_length(n_text - m + 1) bits,
+    for k <= 32 the top k bits of one 32-bit Mersenne-Twister output, and draws
+    again while the value is out of range; so numpy's MT19937, started from the
+    same state, yields the same outputs a block at a time.  Longer texts take
+    synth's loop."""
+    import random
+    n = n_text - m + 1
+    k = n.bit_length()
+    if n < 1 or k > 32:
+        return synth.read_starts(n_text, num, m, seed)
+    st = random.Random(seed).getstate()[1]
+    bg = np.random.MT19937()
+    bg.state = {"bit_generator": "MT19937", "state": {"key": np.array(st[:-1], dtype=np.uint32), "pos": st[-1]}}
+    out, have = np.empty(num, dtype=np.int64), 0
+    while have < num:
+        raw = bg.random_raw(int((num - have) * 1.02 * (1 << k) / n) + 1024) >> np.uint64(32 - k)
+        ok = raw[raw < n][:num - have]
+        out[have:have + ok.size] = ok
+        have += ok.size
+    return out
+
+
+def dump_outputs(d, res: np.ndarray, budget: int = 32 << 20) -> dict:
+    """--dump-outputs: the timed path's results -- what a caller of
+    searchIndexGPU + transferGPUtoCPU receives, [L, R) per read -- as
+    d/intervals.npy, float64 [n, 2] (exact: the bounds are below 2^32).  When
+    all the reads would take more than `budget` bytes, a fixed sample of them
+    (default_rng(0), ascending read numbers, in d/reads_sampled.npy) is kept."""
+    d = Path(d)
+    d.mkdir(parents=True, exist_ok=True)
+    lr = res.reshape(-1, 2)
+    n = lr.shape[0]
+    keep = budget // 16
+    sel = np.arange(n) if n <= keep else np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+    np.save(d / "intervals.npy", lr[sel].astype(np.float64))
+    np.save(d / "reads_sampled.npy", sel.astype(np.float64))
+    return {"dir": str(d), "reads": int(sel.size), "of": int(n), "files": ["intervals.npy", "reads_sampled.npy"]}
 
 
 def _node_shared(D, name: str, nbytes: int, write):
@@ -1278,6 +1347,9 @@ def compact_line(detail: dict, detail_path: str | None) -> dict:
                                        ("shared_gpus", dv.get("shared_devices"))) if x is not None}
     line["configs"] = detail.get("configs") or {}
     line["detail"] = detail_path
+    for k in ("full", "outputs"):
+        if k in detail:
+            line[k] = detail[k]
     if len(json.dumps(line, separators=(",", ":"))) > LINE_MAX:
         line["configs"] = {k: {kk: vv for kk, vv in v.items() if kk != "what"} for k, v in line["configs"].items()}
     if len(json.dumps(line, separators=(",", ":"))) > LINE_MAX:
@@ -1329,12 +1401,13 @@ def main():
     # below from the PCI bus ids and reported, never claimed as N GPUs
     dev = D.local % ndev
     K.set_device(dev)
-    try:
-        import torch
-        if torch.cuda.is_available():
-            torch.cuda.set_device(dev)
-    except Exception:
-        pass
+    if D.world > 1:                    # torch is loaded (Dist): its current device follows the rank's
+        try:
+            import torch
+            if torch.cuda.is_available():
+                torch.cuda.set_device(dev)
+        except Exception:
+            pass
     dev_rows = device_rows(D, dev)
     dev_agg = aggregate_devices(dev_rows)
     if dev_agg["shared_devices"] and D.rank == 0:
@@ -1390,7 +1463,7 @@ def main():
         index_md5_ok = h == synth.MD5["ref3g.k2d64.fmi"]
         log(f"index md5 {h} pinned-ok={index_md5_ok}", brief=True)
     t = time.perf_counter()
-    starts = synth.read_starts(len(text), a.queries, a.qlen, seed=10 + D.rank)
+    starts = read_starts(len(text), a.queries, a.qlen, seed=10 + D.rank)
     reads = synth.gather_reads(text, starts, a.qlen)
     del starts
     log(f"rank {D.rank}: {reads.shape[0]} reads in {time.perf_counter() - t:.1f}s")
@@ -1431,6 +1504,10 @@ def main():
     K.transfer_to_cpu(r)
     d2h_s = time.perf_counter() - t
     res = r.array().copy()
+    dumped = None
+    if a.dump_outputs and D.rank == 0:
+        dumped = dump_outputs(a.dump_outputs, res)
+        log(f"outputs of the last timed step: {dumped}", brief=True)
     results_md5_ok = None
     if pinned and a.qlen == 100 and a.queries == 10_000_000 and D.rank == 0 and not a.no_md5:
         results_md5_ok = synth.results_md5(res) == synth.MD5["res3g.q10M"]
@@ -1454,9 +1531,11 @@ def main():
     ph.mark("parity")
 
     # ---- roofline: algorithmic bytes of the LF kernel ------------------------
-    blocks = K.count_blocks(idx, q)
+    # (a launch of its own over the batch: with --full; without it the line's
+    # roofline keeps the LF time and leaves the byte counts and fractions null)
+    blocks = K.count_blocks(idx, q) if a.full else None
     b_lf = a.k * a.d // 4 + 4                               # bit planes of one block + one counter
-    bytes_alg = blocks * b_lf                               # 36 B x distinct blocks
+    bytes_alg = blocks * b_lf if a.full else None           # 36 B x distinct blocks
     # reported beside it: what the LF kernel also reads per query (the ASCII row
     # when packing is fused into the task kernel, else the packed code words)
     # and the (L, R) it writes
@@ -1466,7 +1545,7 @@ def main():
     q_in = a.qlen if fused else 4 * nwords
     bytes_io = reads.shape[0] * (q_in + 8)
     lf_avg_ms = float(np.mean(lf_ms))
-    achieved = bytes_alg / (lf_avg_ms / 1e3) / 1e9
+    achieved = bytes_alg / (lf_avg_ms / 1e3) / 1e9 if a.full else None
     # traffic per launch from the committed PMC profile of the same config, by
     # the guide's recipe (MI355X_MICROARCH.md HBM section): FETCH_SIZE in its own
     # pass, doubled (gfx950 tallies a 128-B request at 64 B; every request here
@@ -1475,7 +1554,7 @@ def main():
     # from above; no gfx950 counter separates the Infinity-Cache hits.
     traffic, traffic_src, traffic_note, rdreq, replay_pmc = None, None, None, None, None
     tj = Path(a.traffic_json)
-    if tj.exists() and D.world == 1:   # a one-GPU PMC profile says nothing about N > 1 runs
+    if a.full and tj.exists() and D.world == 1:   # a one-GPU PMC profile says nothing about N > 1 runs
         try:
             tr = json.loads(tj.read_text())
             if (tr.get("backend") == a.backend and tr.get("queries") == a.queries and tr.get("ref_size") == a.ref_size
@@ -1489,7 +1568,8 @@ def main():
     # the kernel's own request stream replayed without its LF dependence
     # (kfmi_probe_replay: MID layouts): a measured ceiling for that exact mix
     replay = None
-    if D.world == 1 and D.rank == 0 and a.backend in ("task-mid", "coop-mid") and a.k == 2 and a.d == 64:
+    if (a.full and D.world == 1 and D.rank == 0 and a.backend in ("task-mid", "coop-mid") and a.k == 2
+            and a.d == 64):
         try:
             replay = [K.probe_replay(idx, q, unroll=u, groups=g, reps=5)
                       for u, g in ((0, 1), (0, 2), (1, 1), (1, 2), (2, 2), (4, 2), (8, 2))]
@@ -1530,14 +1610,14 @@ def main():
     rank_rows = D.gather({"ingest": ingest, "rank": D.rank, "device": dev,
                           "pci_bus_id": dev_rows[D.rank]["pci_bus_id"], "queries": int(reads.shape[0]),
                           "lf_ms": round(float(np.mean(lf_ms)), 4), "step_ms": round(float(np.mean(tot_ms)), 4),
-                          "elapsed_s": round(elapsed, 4), "distinct_blocks": int(blocks),
+                          "elapsed_s": round(elapsed, 4), "distinct_blocks": int(blocks) if a.full else None,
                           "parity_ok": parity_ok, "parity_sample": int(ns_par),
                           "results_md5_pinned": results_md5_ok})
     ranks = aggregate_ranks(rank_rows)
 
     extra = {}
     ph.mark("gather")
-    probe = probe_leg() if D.world == 1 and D.rank == 0 else None
+    probe = probe_leg() if a.full and D.world == 1 and D.rank == 0 else None
     ceiling = probe["ceiling_G_lines_per_s"] if probe else PROBE_CEILING_GLINES
     ceiling_src = ((f"gather_probe on this box, this run: the larger of the 3 GB (HBM) and 200 MB "
                     f"(Infinity-Cache-resident, best of {probe['infinity_cache_200MB']['runs']} runs per kind) "
@@ -1575,7 +1655,7 @@ def main():
     if ingest is not None:
         extra["ingest_file"] = ingest          # rank 0's; every rank's is under "ranks"
     cpu = None
-    if D.rank == 0 and D.world == 1 and a.sa_rate:
+    if a.full and D.rank == 0 and D.world == 1 and a.sa_rate:
         # ---- locate: text positions of every [L, R) ---------
         loc = K.locate(idx, r)                                  # warm-up (SA upload)
         loc.close()
@@ -1604,7 +1684,7 @@ def main():
         log(f"locate {extra['locate']}")
         loc.close()
     variants_pmc = pmc100
-    if D.rank == 0 and D.world == 1:
+    if a.full and D.rank == 0 and D.world == 1:
         # ---- other backends (same index, same reads) ------------------------
         for b in [x for x in a.variants.split(",") if x and x != a.backend]:
             try:
@@ -1823,14 +1903,16 @@ def main():
             "ranks_launched": D.world,
             "launcher": os.environ.get("KFMI_BENCH_LAUNCHER", "external" if D.world > 1 else "none"),
             "devices": dict(dev_agg, per_rank=dev_rows),
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+            "roofline": {"bound": "hbm", "achieved": round(achieved, 1) if a.full else None, "peak": HBM_PEAK_GBS,
+                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4) if a.full else None,
+                         "traffic": traffic,
                          "kernel": kernel_prefix(a.backend, a.k, a.d, a.qlen).split("<", 1)[0].replace("kfmi::", "")
                                    + f" {a.backend}, HIP-event average over the timed steps",
                          "launches": launch_spec(a.backend, a.k, a.d, a.qlen, reads.shape[0], a.warmup, a.steps),
                          "bytes_per_launch": bytes_alg, "distinct_blocks": blocks, "bytes_per_block": b_lf,
                          "bytes_per_query_io": q_in + 8,
-                         "achieved_incl_query_io": round((bytes_alg + bytes_io) / (lf_avg_ms / 1e3) / 1e9, 1),
+                         "achieved_incl_query_io": (round((bytes_alg + bytes_io) / (lf_avg_ms / 1e3) / 1e9, 1)
+                                                    if a.full else None),
                          "lf_ms": round(lf_avg_ms, 4), "pack_ms": round(float(np.mean(pack_ms)), 4),
                          "naive_bytes_per_launch": 2 * (a.qlen // a.k) * b_lf * a.queries,
                          "traffic_source": traffic_src,
@@ -1853,7 +1935,7 @@ def main():
                          "fabric_request_bytes_upper_bound": rdreq * 128 if rdreq else None,
                          "line_requests_per_query": round(rdreq / a.queries, 2) if rdreq else None,
                          "line_requests_G_per_s": round(rdreq / (lf_avg_ms / 1e3) / 1e9, 2) if rdreq else None,
-                         "line_request_ceiling_G_per_s": ceiling,
+                         "line_request_ceiling_G_per_s": ceiling if a.full else None,
                          "line_request_ceiling_source": ceiling_src,
                          "line_request_frac": round(rdreq / (lf_avg_ms / 1e3) / 1e9 / ceiling, 3) if rdreq else None,
                          # the same question on the kernel's own fetches (distinct blocks = lines it loads):
@@ -1890,10 +1972,14 @@ def main():
             "device_index_bytes": dev_index_bytes,
             "phases": phases,
             "variants": extra,
+            "full": a.full,
+            "outputs": dumped,
         }
         detail["configs"] = config_rows(detail, a)
-        dpath = write_detail(detail, a.detail, D.world)
+        # a plain run leaves no record beside its line unless --detail names one
+        dpath = write_detail(detail, a.detail, D.world) if a.full or a.detail else None
         line = compact_line(detail, dpath)
+        log(f"phases (s): {ph.rows}", brief=True)
         log(f"detail: {dpath}; line {len(json.dumps(line))} B", brief=True)
         # the line is the last thing on stdout, after everything on stderr
         sys.stderr.flush()

@@ -9,7 +9,7 @@ OUT=$R/gpurun_out
 mkdir -p $OUT
 export TMPDIR=/tmp KFMI_BENCH_LOGDIR=$OUT
 cd /tmp
-CMD="python3 $R/bench.py --gpus 1 --steps 20 --warmup 5"
+CMD="python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --full"
 timeout -k 10 600 $CMD --detail $OUT/bench_${T}_detail.json > $OUT/bench_$T.json 2> $OUT/bench_$T.err || { tail -20 $OUT/bench_$T.err; exit 35; }
 wc -c $OUT/bench_$T.json $OUT/bench_$T.err
 cut -c1-400 $OUT/bench_$T.json

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Every bench row's LF kernel time from a rocprofv3 kernel trace of the same
-bench.py command, and the row's algorithmic-HBM fraction recomputed from it
+bench.py --full command (the rows and the detail file are --full's), and the row's algorithmic-HBM fraction recomputed from it
 (each row's `frac` must reproduce from a rocprof summary).
 
   python scripts/rows_from_trace.py --trace <..._kernel_trace.csv> \

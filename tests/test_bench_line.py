@@ -114,6 +114,47 @@ def test_kernel_prefix_names_the_timed_kernels():
         assert bench.kernel_prefix(b, k, 64, 100) in stats, b
 
 
+@pytest.mark.parametrize("n_text,num,m,seed", [(3_000_000_000, 20_000, 100, 10),     # 32-bit draws, 30 % redrawn
+                                                (1 << 26, 20_000, 100, 11), (1001, 5000, 1, 3), (100, 50, 100, 4),
+                                                (5_000_000_000, 500, 150, 20)])    # past 32 bits: synth's loop
+def test_read_starts_equal_the_recipe(n_text, num, m, seed):
+    """bench.read_starts (block-wise Mersenne Twister) gives synth.read_starts'
+    numbers: the bench's reads stay the md5-pinned ones."""
+    import numpy as np
+    from kstep_fmi import synth
+    got = bench.read_starts(n_text, num, m, seed)
+    assert got.dtype == np.int64 and np.array_equal(got, synth.read_starts(n_text, num, m, seed))
+
+
+def test_plain_run_switches_every_optional_leg_off():
+    """Without --full the legs beside the timed steps are off whatever their
+    own options say; with it the options hold as given."""
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3", "--cpu-sample", "5000"])
+    assert not a.full and a.steps == 7 and a.warmup == 3 and a.dump_outputs is None
+    assert a.no_md5 and a.parity_sample == 0 and a.cpu_sample == 0 and not a.config1 and not a.kstep4
+    assert a.config5_queries == 0 and a.ingest == "off" and a.variants == "" and a.e2e_steps == 0
+    f = bench.parse(["--full", "--cpu-sample", "5000", "--dump-outputs", "out"])
+    assert f.full and f.cpu_sample == 5000 and f.parity_sample == 100_000 and f.kstep4 and f.config1
+    assert not f.no_md5 and f.config5_queries == 10_000_000 and "task-ac" in f.variants and f.dump_outputs == "out"
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """--dump-outputs: float64 (exact for u32 bounds) [L, R) rows; past the
+    byte budget the same seeded sample of the reads on every call."""
+    import numpy as np
+    res = np.random.default_rng(5).integers(0, 1 << 32, size=2 * 5000, dtype=np.uint64).astype(np.uint32)
+    info = bench.dump_outputs(tmp_path / "a", res)
+    lr = np.load(tmp_path / "a" / "intervals.npy")
+    assert info["reads"] == 5000 and lr.dtype == np.float64 and np.array_equal(lr, res.reshape(-1, 2))
+    assert np.array_equal(np.load(tmp_path / "a" / "reads_sampled.npy"), np.arange(5000))
+    for d in ("b", "c"):
+        assert bench.dump_outputs(tmp_path / d, res, budget=16 * 1000)["reads"] == 1000
+    sel = np.load(tmp_path / "b" / "reads_sampled.npy").astype(np.int64)
+    assert sel.size == 1000 and np.all(np.diff(sel) > 0)
+    assert np.array_equal(sel, np.load(tmp_path / "c" / "reads_sampled.npy"))
+    assert np.array_equal(np.load(tmp_path / "b" / "intervals.npy"), res.reshape(-1, 2)[sel])
+
+
 STUB = textwrap.dedent(r"""
     import json, os, sys
     sys.path.insert(0, %(repo)r); sys.path.insert(0, %(pkg)r)
