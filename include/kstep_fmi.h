@@ -173,11 +173,40 @@ int32_t     kfmi_search_cpu(void *index, void *queries, void *results, int32_t n
 /* ftab (Bowtie-style jump start; not in the reference): every backend looks
  * up [L, R) after the first `bases` bases of each query in a table of all
  * 4^bases codes (8 B each: 134 MB at 12) built on the device with the search's
- * own LF steps, then continue from there -- results are unchanged.  0 = off
- * (default; KFMI_FTAB, read once at the first search, sets it process-wide),
- * at most 16, a multiple of K to
- * take effect; per calling thread like the backend. */
+ * own LF steps, then continue from there -- results are unchanged.  The
+ * first bases / K K-steps of a read depend only on the index and on the read's
+ * last `bases` bases, and the index stays the same from call to call, so the
+ * table is a default like the upload's own re-layout and remainder table, not
+ * an option: with KFMI_FTAB unset and no call here the setting is
+ * KFMI_FTAB_AUTO -- kfmi_ftab_auto_bases() of the index's rows, its K and a
+ * quarter of the device memory free when the table is allocated, built during
+ * transferCPUtoGPU (on every member of a device group) so that no search call
+ * pays for it; a failed allocation or a budget too small steps the auto table
+ * down by K bases or switches it off, never an error.  0 = off: the pure
+ * walk of every K-step, as every comparison row is taken.  An explicit count
+ * is at most 16 and a multiple of K to take effect; its table is built at the
+ * first search that needs it and KFMI_E_DEVICE_ALLOC is returned when it does
+ * not fit.  KFMI_FTAB (read once at the first search; a count, 0 or "auto")
+ * sets it process-wide; the setter is per calling thread like the backend.
+ * Memory: 8 * 4^bases bytes per uploaded index and device, next to the index
+ * copy -- 34 GB at 16 bases (a 3 Gbase index), 134 MB at 12 (64 Mbase).  A
+ * transfer that replaces a handle's device copy (another backend or device)
+ * frees the old copy's tables before it allocates the new copy. */
+#define KFMI_FTAB_AUTO 0xFFFFFFFFu
 int32_t     kfmi_set_ftab(uint32_t bases);
+/* The auto rule (pure host arithmetic, no device): the largest N <= 16 that is
+ * a multiple of K with 4^N <= 2 * rows (rows = n + 1; deeper tables are mostly
+ * empty intervals), stepped down by K while 8 * 4^N exceeds budget_bytes; 0
+ * (off) for an index of fewer than 8 rows, K outside 1..4 or a budget below
+ * the smallest table. */
+uint32_t    kfmi_ftab_auto_bases(uint64_t rows, uint32_t K, uint64_t budget_bytes);
+/* Test knob, process-wide: the byte budget of the auto rule in place of a
+ * quarter of the free device memory; KFMI_FTAB_BUDGET_FREE returns to that. */
+#define KFMI_FTAB_BUDGET_FREE 0xFFFFFFFFFFFFFFFFull
+int32_t     kfmi_set_ftab_budget(uint64_t bytes);
+/* Bytes of the jump-start tables the handle's device copies hold (all members
+ * of a device group); kfmi_device_index_bytes counts the index copies only. */
+uint64_t    kfmi_device_ftab_bytes(void *index);
 /* Test knobs of the search path (not in the reference), process-wide; their
  * environment variables are read once, at the first search, and these setters
  * switch them afterwards.  Split class (KFMI_SPLIT): the fetch form the task

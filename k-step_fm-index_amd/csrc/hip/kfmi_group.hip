@@ -207,6 +207,7 @@ int32_t group_transfer(kfmi_fmi_t* f, kfmi_qrys_t* q, kfmi_res_t* r, const int* 
       const auto t0 = clk::now();
       double setup_ms = 0;
       group_free_index(f);
+      drop_ftabs(f->dev);   /* the single-device copy goes below: its tables' memory first */
       g = new (std::nothrow) GroupIndex();
       if (!g) return KFMI_E_ALLOCATING_FMI;
       g->n = n;
@@ -240,6 +241,13 @@ int32_t group_transfer(kfmi_fmi_t* f, kfmi_qrys_t* q, kfmi_res_t* r, const int* 
         if (g->st[i]) {
           (void) hipSetDevice(devs[i]);
           if (hipStreamSynchronize(g->st[i]) != hipSuccess && !err) err = KFMI_E_KERNEL;
+        }
+      /* the auto jump-start table of every replica, built on its own device
+       * from its own copy (part of the upload, as on a single device) */
+      if (ftab_bases() == KFMI_FTAB_AUTO)
+        for (int i = 0; i < n && !err; ++i) {
+          if (hipSetDevice(devs[i]) != hipSuccess) err = KFMI_E_NO_DEVICE;
+          if (!err) err = auto_ftab(g->di[i], g->st[i], nullptr);
         }
       if (err) {
         group_free_index(f);

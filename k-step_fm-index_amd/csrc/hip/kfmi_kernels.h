@@ -302,22 +302,33 @@ __global__ __launch_bounds__(256) void task_kernel(IdxArgs ix, const uint32_t* _
  * form returned wrong entries; the cause was the 16-byte load at 8-byte
  * alignment LLVM formed from two 8-byte plane loads, which
  * load_words now keeps out, so the build is lf_stream's again and
- * test_ftab_table_every_entry checks its tables entry by entry. */
+ * test_ftab_table_every_entry checks its tables entry by entry.
+ *
+ * Level by level, in place, one launch per level t = 0 .. ftab_steps-1
+ * (launch_ftab): the entries of the `parents` = NC^t code streams of t K-steps
+ * sit at out[0 .. parents) (level 0: the one interval [0, n+1), not stored),
+ * and the entry of v followed by K-step c is out[v | c << 2Kt].  The thread of
+ * parent v reads its own [L, R) first and then writes its NC children: child 0
+ * overwrites only that parent's slot, every other child lands at or past
+ * `parents`, where this level reads nothing.  All NC children of a parent step
+ * from the same two rows, so they read the same lines: the deepest level
+ * fetches NC times fewer lines than a walk per entry, and no level repeats the
+ * steps of the ones before it. */
 template <class G>
-__global__ __launch_bounds__(256) void ftab_build_kernel(IdxArgs ix, uint32_t fsteps, uint64_t n,
-                                                         uint2* __restrict__ out)
+__global__ __launch_bounds__(256) void ftab_level_kernel(IdxArgs ix, uint32_t t, uint64_t parents, uint2* out)
 {
-  /* grid-stride: 4^16 entries exceed the 2^32 work-items of one dispatch */
-  for (uint64_t v = (uint64_t) blockIdx.x * 256 + threadIdx.x; v < n; v += (uint64_t) gridDim.x * 256) {
-    uint32_t L = 0, R = ix.bwtsize;
-    for (uint32_t t = 0; t < fsteps; ++t) {
-      const uint32_t c = (uint32_t) (v >> (2 * G::K * t)) & (uint32_t) (G::NC - 1);
+  /* grid-stride: the launch's grid is capped (grid_blocks) */
+  for (uint64_t v = (uint64_t) blockIdx.x * 256 + threadIdx.x; v < parents; v += (uint64_t) gridDim.x * 256) {
+    uint2 lr = make_uint2(0u, ix.bwtsize);
+    if (t) lr = out[v];
+#pragma unroll 1
+    for (uint32_t c = 0; c < (uint32_t) G::NC; ++c) {
       uint32_t sx[2 * G::K];
       plane_xor<G::K>(c, sx);
-      L = lf_stream<G>(ix, L, c, sx);
-      R = lf_stream<G>(ix, R, c, sx);
+      const uint32_t L = lf_stream<G>(ix, lr.x, c, sx);
+      const uint32_t R = lf_stream<G>(ix, lr.y, c, sx);
+      out[v | ((uint64_t) c << (2 * G::K * t))] = make_uint2(L, R);
     }
-    out[v] = make_uint2(L, R);
   }
 }
 
@@ -660,10 +671,17 @@ static hipError_t launch_locate(const SearchLaunch& a)
 template <class G>
 static hipError_t launch_ftab(const SearchLaunch& a)
 {
-  const uint64_t blocks = (a.ftab_n + 255) / 256;
-  hipLaunchKernelGGL((ftab_build_kernel<G>), dim3(grid_blocks(blocks, 1u << 20)), dim3(256), 0,
-                     a.st, a.ix, a.ftab_steps, a.ftab_n, a.ftab_out);
-  return hipGetLastError();
+  /* one launch per level, in stream order: level t reads what level t-1 wrote */
+  uint64_t parents = 1;
+  for (uint32_t t = 0; t < a.ftab_steps; ++t, parents <<= 2 * G::K) {
+    if ((parents << (2 * G::K)) > a.ftab_n) return hipErrorInvalidValue;   /* the children stay inside the table */
+    const uint64_t blocks = (parents + 255) / 256;
+    hipLaunchKernelGGL((ftab_level_kernel<G>), dim3(grid_blocks(blocks, 1u << 20)), dim3(256), 0, a.st, a.ix, t,
+                       parents, a.ftab_out);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 template <class G>

@@ -52,6 +52,9 @@ struct kfmi_dev_index {
    * kfmi_set_ftab values never free a table another kernel reads) */
   uint2* ftab[17] = {};
   std::mutex ftab_mu;
+  /* bases of the auto table (KFMI_FTAB_AUTO), decided once per device copy
+   * under ftab_mu (auto_ftab): -1 not yet, 0 none */
+  int ftab_auto = -1;
   /* remainder tables: [L, R) of every r-base read suffix, r = m % K in 1..3
    * (same lifetime rule as the ftabs, same mutex) */
   uint2* rtab[4] = {};
@@ -133,6 +136,11 @@ hipError_t dispatch(Op op, uint32_t K, uint32_t nb, int lay, const SearchLaunch&
                     unsigned long long* d_total = nullptr);
 IdxArgs idx_args(const kfmi_dev_index* di);
 int32_t use_ftab(kfmi_dev_index* di, hipStream_t st, IdxArgs& ix, uint32_t bases);
+/* decides and builds the index's auto table once (device `di->device` current);
+ * *bases (may be null) = its base count, 0 when it has none */
+int32_t auto_ftab(kfmi_dev_index* di, hipStream_t st, uint32_t* bases);
+/* frees the tables of a device copy about to be replaced (handle locked exclusively) */
+void drop_ftabs(kfmi_dev_index* di);
 /* reads with m % K = rem != 0: layouts that take the remainder
  * table, and the table of an index (built on first use; clears the ftab) */
 bool rem_supported(int layout);

@@ -42,7 +42,7 @@ static thread_local bool t_backend_implicit = true;   /* neither KFMI_BACKEND no
 thread_local int t_device = -1;
 thread_local int32_t t_last_error = KFMI_SUCCESS;
 thread_local double t_ms[3] = {0, 0, 0};
-static thread_local int t_ftab = -1;   /* ftab bases for the task kernels; -1: KFMI_FTAB, else 0 */
+static thread_local int t_ftab = -1;   /* ftab bases; -1: KFMI_FTAB, else auto; -2: auto (kfmi_set_ftab) */
 
 static int backend_from_name(const char* n)
 {
@@ -141,20 +141,42 @@ extern "C" void kfmi_set_last_error(int32_t e) { t_last_error = e; }
 
 extern "C" int32_t kfmi_set_ftab(uint32_t bases)
 {
-  if (bases > 16) return KFMI_E_BAD_ARGUMENT;
-  t_ftab = (int) bases;
+  if (bases > 16 && bases != KFMI_FTAB_AUTO) return KFMI_E_BAD_ARGUMENT;
+  t_ftab = bases == KFMI_FTAB_AUTO ? -2 : (int) bases;
   return KFMI_SUCCESS;
 }
 
+/* The calling thread's setting: a base count, 0 (off) or KFMI_FTAB_AUTO, which
+ * use_ftab resolves per index. */
 uint32_t ftab_bases(void)
 {
   if (t_ftab >= 0) return (uint32_t) t_ftab;
+  if (t_ftab == -2) return KFMI_FTAB_AUTO;
   static const uint32_t env = [] {   /* KFMI_FTAB, read once per process */
     const char* e = getenv("KFMI_FTAB");
-    const int v = e ? atoi(e) : 0;
+    if (!e || !*e || !strcmp(e, "auto")) return (uint32_t) KFMI_FTAB_AUTO;
+    const int v = atoi(e);
     return v > 0 && v <= 16 ? (uint32_t) v : 0u;
   }();
   return env;
+}
+
+/* The auto rule (kstep_fmi.h): host arithmetic only, so a CPU test calls it. */
+extern "C" uint32_t kfmi_ftab_auto_bases(uint64_t rows, uint32_t K, uint64_t budget_bytes)
+{
+  if (K < 1 || K > 4 || rows < 8) return 0;
+  uint32_t n = 16 - 16 % K;
+  while (n && (1ull << (2 * n)) > 2 * rows) n -= K;
+  while (n && (8ull << (2 * n)) > budget_bytes) n -= K;
+  return n;
+}
+
+static std::atomic<uint64_t> g_ftab_budget{KFMI_FTAB_BUDGET_FREE};
+
+extern "C" int32_t kfmi_set_ftab_budget(uint64_t bytes)
+{
+  g_ftab_budget.store(bytes, std::memory_order_relaxed);
+  return KFMI_SUCCESS;
 }
 
 /* Test knobs of the search path: read from the environment once per process
@@ -1045,7 +1067,8 @@ int32_t upload_index(kfmi_fmi_t* f, int backend, int dev, DevCtx* ctx, kfmi_dev_
  *    18.93 -> 17.94 at 150 bp; the retired packed layout 14.0 -> 13.3).
  * profiles/r02/sweep_split_r2ah.jsonl, sweep_split150_r2aj.jsonl; the asm
  * forms: profiles/r03/sweep_r3n.jsonl, sweep150_r3n.jsonl.  The ftab lookup
- * (one gather per read) is never split: that measured slower.
+ * (one gather per read) is never split: that measured slower on the 2.1 GB
+ * table and no faster on the 34 GB one.
  * KFMI_SPLIT=1|2|4 / kfmi_set_split_class (a test knob) answers in place of the table size, so that
  * a small test index runs the fetch form a table of that size class gets
  * (launch_task: one form per geometry and class). */
@@ -1435,32 +1458,101 @@ int32_t use_rtab(kfmi_dev_index* di, hipStream_t st, IdxArgs& ix, uint32_t rem)
   return KFMI_SUCCESS;
 }
 
-/* The ftab of `bases` bases, (re)built on the device from the uploaded layout
- * with the search's own LF steps; sets ix.ftab (null when off or when bases is
- * not a multiple of K). */
+/* The table of `bases` bases built into di->ftab[bases] (caller holds ftab_mu):
+ * one launch per level on `st` (launch_ftab), waited for. */
+static int32_t build_ftab(kfmi_dev_index* di, hipStream_t st, uint32_t bases)
+{
+  uint2* t = nullptr;
+  if (hipMalloc((void**) &t, 8ull << (2 * bases)) != hipSuccess) {
+    (void) hipGetLastError();
+    return KFMI_E_DEVICE_ALLOC;
+  }
+  SearchLaunch a{};
+  a.st = st;
+  a.ix = idx_args(di);
+  a.ftab_out = t;
+  a.ftab_steps = bases / di->K;
+  a.ftab_n = 1ull << (2 * bases);
+  if (dispatch(Op::Ftab, di->K, di->nb, di->layout, a) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+    (void) hipFree(t);
+    return KFMI_E_KERNEL;
+  }
+  di->ftab[bases] = t;   /* published complete; never replaced */
+  return KFMI_SUCCESS;
+}
+
+/* The auto table of an index (KFMI_FTAB_AUTO), decided once per device copy:
+ * kfmi_ftab_auto_bases of its rows, K and the budget -- a quarter of the
+ * device memory free right now, or kfmi_set_ftab_budget's bytes -- and, when
+ * that table cannot be allocated, K bases fewer until one can or none is left.
+ * Never an allocation error: the search then walks every step.  Called from
+ * the uploads (transferCPUtoGPU, group_transfer) when the caller's setting is
+ * auto, so that no search pays for the build, and from use_ftab for an index
+ * uploaded under another setting. */
+int32_t auto_ftab(kfmi_dev_index* di, hipStream_t st, uint32_t* bases)
+{
+  std::lock_guard<std::mutex> lk(di->ftab_mu);
+  if (di->ftab_auto < 0) {
+    uint64_t budget = g_ftab_budget.load(std::memory_order_relaxed);
+    if (budget == KFMI_FTAB_BUDGET_FREE) {
+      size_t free_b = 0, total_b = 0;
+      if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
+        (void) hipGetLastError();
+        free_b = 0;
+      }
+      budget = (uint64_t) free_b / 4;
+    }
+    uint32_t n = kfmi_ftab_auto_bases(di->bwtsize, di->K, budget);
+    for (; n; n -= di->K) {
+      if (di->ftab[n]) break;   /* an explicit setting built it already */
+      const int32_t e = build_ftab(di, st, n);
+      if (!e) break;
+      if (e != KFMI_E_DEVICE_ALLOC) return e;
+    }
+    di->ftab_auto = (int) n;
+  }
+  if (bases) *bases = (uint32_t) di->ftab_auto;
+  return KFMI_SUCCESS;
+}
+
+/* Frees the jump-start tables of a device copy that is about to be replaced
+ * (caller holds the handle's exclusive lock: no search reads them).  They are
+ * derived data, up to 34 GB each, and the replacing upload needs the memory:
+ * a K = 4 copy re-laid for another backend holds two 96 GB layouts for a
+ * moment.  Should that upload fail, the old copy stays searchable and builds
+ * its tables again on demand. */
+void drop_ftabs(kfmi_dev_index* di)
+{
+  if (!di) return;
+  std::lock_guard<std::mutex> lk(di->ftab_mu);
+  if (di->device >= 0) (void) hipSetDevice(di->device);
+  for (uint2*& t : di->ftab)
+    if (t) {
+      (void) hipFree(t);
+      t = nullptr;
+    }
+  di->ftab_auto = -1;
+}
+
+/* The ftab of `bases` bases (KFMI_FTAB_AUTO: the index's auto table), built
+ * on the device from the uploaded layout with the search's own LF steps when
+ * it is not there yet; sets ix.ftab (null when off or when bases is not a
+ * multiple of K). */
 int32_t use_ftab(kfmi_dev_index* di, hipStream_t st, IdxArgs& ix, uint32_t bases)
 {
   ix.ftab = nullptr;
   ix.ftab_steps = 0;
   ix.ftab_mask = 0;
+  if (bases == KFMI_FTAB_AUTO) {
+    const int32_t e = auto_ftab(di, st, &bases);
+    if (e) return e;
+  }
   if (!bases || bases % di->K || bases > 16) return KFMI_SUCCESS;
   {
     std::lock_guard<std::mutex> lk(di->ftab_mu);
     if (!di->ftab[bases]) {
-      const uint64_t n = 1ull << (2 * bases);
-      uint2* t = nullptr;
-      if (hipMalloc((void**) &t, 8 * n) != hipSuccess) return KFMI_E_DEVICE_ALLOC;
-      SearchLaunch a{};
-      a.st = st;
-      a.ix = idx_args(di);
-      a.ftab_out = t;
-      a.ftab_steps = bases / di->K;
-      a.ftab_n = n;
-      if (dispatch(Op::Ftab, di->K, di->nb, di->layout, a) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        (void) hipFree(t);
-        return KFMI_E_KERNEL;
-      }
-      di->ftab[bases] = t;   /* published complete; never replaced */
+      const int32_t e = build_ftab(di, st, bases);
+      if (e) return e;
     }
   }
   ix.ftab = di->ftab[bases];
@@ -1684,7 +1776,11 @@ extern "C" int32_t transferCPUtoGPU(void* index, void* queries, void* results)
       std::unique_lock<RwLock> ul(index_lock(f));
       if (!fits()) {
         group_free_index(f);   /* one mode per handle */
+        drop_ftabs(f->dev);    /* the copy being replaced: its tables' memory goes to the new one */
+        (void) hipSetDevice(dev);
         err = upload_index(f, backend, dev, ctx);
+        /* the auto jump-start table is part of the upload, like the re-layout */
+        if (!err && ftab_bases() == KFMI_FTAB_AUTO) err = auto_ftab(f->dev, ctx->st, nullptr);
         if (err) return err;
       }
       qk = device_steps(f);
@@ -1962,6 +2058,30 @@ extern "C" uint64_t kfmi_device_index_bytes(void* index)
   }
   if (!f || !f->dev) return 0;
   return f->dev->ent_bytes + f->dev->sa_bytes;
+}
+
+static uint64_t ftab_bytes_of(kfmi_dev_index* di)
+{
+  std::lock_guard<std::mutex> lk(di->ftab_mu);
+  uint64_t b = 0;
+  for (uint32_t n = 1; n <= 16; ++n)
+    if (di->ftab[n]) b += 8ull << (2 * n);
+  return b;
+}
+
+extern "C" uint64_t kfmi_device_ftab_bytes(void* index)
+{
+  kfmi_fmi_t* f = (kfmi_fmi_t*) index;
+  if (!f) return 0;
+  std::shared_lock<RwLock> lk(index_lock(f));
+  uint64_t b = 0;
+  if (f->grp) {
+    const GroupIndex* g = (const GroupIndex*) f->grp;
+    for (int i = 0; i < g->n; ++i) b += ftab_bytes_of(g->di[i]);
+  } else if (f->dev) {
+    b = ftab_bytes_of(f->dev);
+  }
+  return b;
 }
 
 }  // namespace kfmi

@@ -118,7 +118,9 @@ def load() -> ctypes.CDLL:
         "kfmi_get_devices": (i32, [ctypes.POINTER(ctypes.c_int32), i32]),
         "kfmi_build_index_ex": (i32, [vp, u64, u32, u32, u32, i32, pvp]),
         "kfmi_set_ftab": (i32, [u32]),
-        "kfmi_set_split_class": (i32, [u32]),
+        "kfmi_ftab_auto_bases": (u32, [u64, u32, u64]),
+        "kfmi_set_ftab_budget": (i32, [u64]),
+        "kfmi_device_ftab_bytes": (u64, [vp]),        "kfmi_set_split_class": (i32, [u32]),
         "kfmi_set_fused": (i32, [i32]),
         "kfmi_set_walk_check": (i32, [u32]),
         "kfmi_walk_check_last": (i32, []),
@@ -159,9 +161,25 @@ def get_backend() -> str:
     return load().kfmi_get_backend().decode()
 
 
-def set_ftab(bases: int) -> None:
-    """Bowtie-style jump-start table of `bases` bases for the task backends (0 = off)."""
-    _check(load().kfmi_set_ftab(int(bases)), f"set_ftab({bases})")
+FTAB_AUTO = 0xFFFFFFFF
+
+
+def set_ftab(bases) -> None:
+    """Jump-start table of `bases` bases (0 = off: the pure walk), or "auto"
+    (the default): sized per index by ftab_auto_bases and built at upload."""
+    n = FTAB_AUTO if bases == "auto" else int(bases)
+    _check(load().kfmi_set_ftab(n), f"set_ftab({bases})")
+
+
+def ftab_auto_bases(rows: int, k: int, budget_bytes: int) -> int:
+    """The auto rule: table bases for an index of `rows` (n + 1) rows and K = k."""
+    return int(load().kfmi_ftab_auto_bases(int(rows), int(k), int(budget_bytes)))
+
+
+def set_ftab_budget(nbytes) -> None:
+    """Byte budget of the auto rule (process-wide test knob); None = a quarter
+    of the free device memory."""
+    _check(load().kfmi_set_ftab_budget(0xFFFFFFFFFFFFFFFF if nbytes is None else int(nbytes)), "set_ftab_budget")
 
 
 def set_split_class(cls: int) -> None:
@@ -358,6 +376,10 @@ class Index(_Handle):
 
     def device_bytes(self) -> int:
         return int(load().kfmi_device_index_bytes(self._p))
+
+    def ftab_bytes(self) -> int:
+        """Bytes of the jump-start tables beside the device copies (not in device_bytes)."""
+        return int(load().kfmi_device_ftab_bytes(self._p))
 
     def sa(self):
         """(rate, uint32 view of the row-sampled suffix array); (0, empty) when absent."""

@@ -18,6 +18,7 @@ from kstep_fmi import synth  # noqa: E402
 
 K.load()
 K.set_device(0)
+K.set_ftab(0)   # the plain kernel: every K-step walked, no jump-start table
 text = synth.text_3g()
 reads = synth.gather_reads(text, synth.read_starts(len(text), 10_000_000, 100, 10), 100)
 idx = {2: K.Index.build(text, k=2, d=64, gpu=True), 4: K.Index.build(text, k=4, d=64, gpu=True, host_image=False)}

@@ -35,6 +35,7 @@ def main():
     a = ap.parse_args()
     K.load()
     K.set_device(0)
+    K.set_ftab(0)   # the plain kernel: every K-step walked, no jump-start table
     text = synth.text_3g()
     idx = K.Index.build(text, k=2, d=64, gpu=True, host_image=False)
     for m in [int(x) for x in a.lens.split(",")]:

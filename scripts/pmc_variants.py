@@ -47,9 +47,13 @@ def main():
     p.add_argument("--queries", type=int, default=10_000_000)
     p.add_argument("--qlen", type=int, default=100, help="150: config #5's shard shape")
     p.add_argument("--seed", type=int, default=10, help="read seed (bench: 10 + rank main leg, 20 + rank config #5)")
+    p.add_argument("--ftab", default="0",
+                   help="jump-start table: 0 = the plain kernel, as bench.py times its variant rows (default); "
+                        "'auto' = the library's default, for the headline's passes (--backends task-mid); or a base count")
     a = p.parse_args()
     K.load()
     K.set_device(0)
+    K.set_ftab("auto" if a.ftab == "auto" else int(a.ftab))
     text = synth.text_3g(a.ref_size) if a.ref_size == 3_000_000_000 else \
         b"".join(synth.text_chunks(a.ref_size))
     reads = synth.gather_reads(text, synth.read_starts(len(text), a.queries, a.qlen, seed=a.seed), a.qlen)

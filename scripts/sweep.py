@@ -53,6 +53,7 @@ def main():
 
     K.load()
     K.set_device(0)
+    K.set_ftab(0)   # the plain kernel: every K-step walked, no jump-start table
     t = time.perf_counter()
     text = synth.text_3g(a.ref_size) if a.ref_size == 3_000_000_000 else \
         np.random.default_rng(1).choice(np.frombuffer(b"ACGT", dtype=np.uint8), size=a.ref_size).tobytes()
