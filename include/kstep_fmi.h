@@ -207,6 +207,50 @@ int32_t     kfmi_set_ftab_budget(uint64_t bytes);
 /* Bytes of the jump-start tables the handle's device copies hold (all members
  * of a device group); kfmi_device_index_bytes counts the index copies only. */
 uint64_t    kfmi_device_ftab_bytes(void *index);
+/* Skip table (not in the reference): once a search interval is the single row
+ * [i, i+1), its next 16 bases can keep it non-empty in one way only -- they
+ * must equal the 16 text bases before suffix SA[i] -- and then the interval is
+ * [LF^J(i), LF^J(i)+1) after J = 16 / K K-steps.  Both are properties of row i,
+ * so a table of 8 B per BWT row ({row, 32-bit code of those J steps}), built on
+ * the device at upload from the search's own steps, replaces J dependent index
+ * lines by one lookup.  A read whose next 16 bases differ from the entry (or
+ * whose entry is marked invalid: the steps pass a '$' row) takes the ordinary
+ * K-steps from the state it had, so results stay bit for bit what the walk
+ * gives, empty intervals included.  The gain belongs to reads whose walk stays
+ * on one row -- exact, locally unique matches, the seeding case; a read in a
+ * repeat walks until its interval narrows, a read with a mismatch pays one
+ * wasted lookup and walks as before.
+ *   Used by the per-lane search kernels (task backends) with in-kernel packing
+ * (reads of up to 256 bases) at K = 1, 2; the coop backends, K = 3 / 4, longer
+ * reads, locate and the statistics calls ignore it, and no table is built for
+ * an index uploaded for them.
+ *   kfmi_set_skip (per calling thread) / KFMI_SKIP (read once; 0, 1 or "auto"):
+ * 0 = off; KFMI_SKIP_AUTO (the default) = in effect exactly when the ftab
+ * setting is KFMI_FTAB_AUTO too, so kfmi_set_ftab(0) keeps meaning the pure
+ * walk of every K-step and an explicit count the walk after that one table;
+ * the table is then built inside transferCPUtoGPU after the auto ftab (on
+ * every member of a device group) when kfmi_skip_auto() allows it, and a
+ * failed allocation leaves it out, never an error; 1 = on whatever the ftab
+ * setting: built at the first search, KFMI_E_DEVICE_ALLOC when it does not fit.
+ * Memory: 8 B x rows next to the index copy (24 GB at 3 Gbase) and the same
+ * again while it is built; freed with the jump-start tables. */
+#define KFMI_SKIP_AUTO 0xFFFFFFFFu
+int32_t     kfmi_set_skip(uint32_t mode);
+/* The calling thread's setting resolved against its ftab setting: 0 = off,
+ * 1 = on (explicit), 2 = auto and in effect. */
+uint32_t    kfmi_skip_in_effect(void);
+/* The auto rule (pure host arithmetic): 1 when K is 1 or 2, 8 <= rows < 2^32
+ * and the table with its transient twin, 16 * rows bytes, is within
+ * budget_bytes (a quarter of the free device memory, or kfmi_set_ftab_budget's
+ * bytes); else 0. */
+uint32_t    kfmi_skip_auto(uint64_t rows, uint32_t K, uint64_t budget_bytes);
+/* Bytes of the skip tables the handle's device copies hold (all members of a
+ * device group); not part of kfmi_device_ftab_bytes or kfmi_device_index_bytes. */
+uint64_t    kfmi_device_skip_bytes(void *index);
+/* Test accessor: the single-device copy's table copied to out[entries] (8 B
+ * each: u32 row, u32 code; row 0xFFFFFFFF = no skip from this row); entries
+ * must be its row count n + 1; *steps (may be null) = J. */
+int32_t     kfmi_device_skip_table(void *index, void *out, uint64_t entries, uint32_t *steps);
 /* Test knobs of the search path (not in the reference), process-wide; their
  * environment variables are read once, at the first search, and these setters
  * switch them afterwards.  Split class (KFMI_SPLIT): the fetch form the task

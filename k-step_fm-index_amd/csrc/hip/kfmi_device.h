@@ -123,7 +123,17 @@ struct IdxArgs {
   // next step's loads inside the table when the counters or '$' rows of a
   // loaded file are corrupt (a wrapped or oversized counter).
   uint32_t lf_cap;
+  // skip table (DESIGN.md 5a'): entry i = {row, code} of the one-row interval
+  // [i, i+1) -- the row after skip_steps = 16/K K-steps and the code stream of
+  // those steps (step t at bits 2K*t); row = SKIP_NONE where the steps leave
+  // one row or pass a '$' row.  null = off.  Fused task kernels at K <= 2 only.
+  // skip_split: the table's gather issued as four 16-lane groups (the table's
+  // own size class, split_for)
+  const uint2* __restrict__ skip;
+  uint32_t skip_rows, skip_steps, skip_split;
 };
+
+constexpr uint32_t SKIP_NONE = 0xFFFFFFFFu;
 
 typedef unsigned int v4u __attribute__((ext_vector_type(4)));
 typedef unsigned int v2u __attribute__((ext_vector_type(2)));

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <algorithm>
 
 #include "kfmi_device.h"
 #include "kfmi_grid.h"
@@ -195,7 +196,85 @@ __device__ __forceinline__ void fetch_ends_split(const IdxArgs& ix, const uint32
   }
 }
 
-template <class G, int QPT, int MAXW, int SPLIT = 1>
+/* The walk of the fused task kernel with the skip table (IdxArgs::skip,
+ * DESIGN.md 5a'): every lane keeps its own step position `pos`, and each
+ * round of the wave-uniform loop a lane takes either one table lookup or one
+ * ordinary K-step -- one line either way, issued before anything waits, so a
+ * round is one memory round trip for the whole wave.
+ *   A lane looks up skip[L] when its interval is the one row [L, L+1), L is a
+ * table row and J = skip_steps more steps remain.  The entry holds the code
+ * stream of the only J steps that keep that row's interval non-empty and the
+ * row they end in; when it equals the read's next 32 code bits the lane is at
+ * [row, row+1) J steps later, exactly as the walk would be (the entry is the
+ * composition of the search's own J steps, skip_level0_kernel).  Otherwise
+ * the lane walks on from the state it had and never looks up again: the walk
+ * empties the interval within those J steps, and a lookup from any row on the
+ * way compares a window that still holds the differing step.
+ *   The code words live in LDS after the staging (64 lanes x MAXW words per
+ * wave, word-major so a wave's reads of one word index hit 64 banks): `pos`
+ * differs per lane, and a register array indexed by it would go to scratch.
+ * Lanes only read what they wrote themselves, so no barrier follows. */
+template <class G, int MAXW, int SPLIT>
+__device__ __forceinline__ void skip_walk(const IdxArgs& ix, const uint32_t (&cw)[MAXW], uint32_t steps, uint32_t pos,
+                                          uint32_t& Lq, uint32_t& Rq)
+{
+  static_assert(G::K <= 2 && MAXW > 0, "skip table: fused task kernels at K <= 2");
+  extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  uint32_t* cl = reinterpret_cast<uint32_t*>(stage) + wv * (64u * MAXW) + lane;
+#pragma unroll
+  for (int k = 0; k < MAXW; ++k) cl[64 * k] = cw[k];
+  const uint32_t J = ix.skip_steps;
+  const int grp = (int) lane / 16;
+  uint32_t L[1] = {Lq}, R[1] = {Rq};
+  bool dead = false;   /* a lookup differed: the ordinary steps from here on */
+  while (__ballot(pos < steps)) {
+    const bool act = pos < steps;
+    const uint32_t bit = pos * (2u * G::K), k = bit >> 5;
+    const uint32_t lo = k < (uint32_t) MAXW ? cl[64u * k] : 0u;
+    const uint32_t hi = k + 1u < (uint32_t) MAXW ? cl[64u * (k + 1u)] : 0u;
+    const uint32_t code = __builtin_amdgcn_alignbit(hi, lo, bit & 31u);   /* the stream from step `pos` on */
+    const bool one = act && !dead && R[0] == L[0] + 1u && L[0] < ix.skip_rows && pos + J <= steps;
+    uint2 e = make_uint2(SKIP_NONE, 0u);
+    if (ix.skip_split == 4u) {   /* wave-uniform: at most 16 pages per gather instruction */
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+        if (one && grp == g) e = ix.skip[L[0]];
+    } else if (one) {
+      e = ix.skip[L[0]];
+    }
+    if (act && !one) {
+      uint32_t c[1] = {code & (uint32_t) (G::NC - 1)};
+      uint32_t sx[2 * G::K];
+      plane_xor<G::K>(c[0], sx);
+      if constexpr (G::SMALL) {
+        Blk<G> kl[1], kr[1];
+        fetch_ends_split<G, 1, SPLIT>(ix, L, R, c, kl, kr);
+        L[0] = lf_from_block<G>(ix, kl[0], L[0], c[0], sx);
+        R[0] = lf_from_block<G>(ix, kr[0], R[0], c[0], sx);
+      } else {
+        L[0] = lf_stream<G>(ix, L[0], c[0], sx);
+        R[0] = lf_stream<G>(ix, R[0], c[0], sx);
+      }
+      ++pos;
+    }
+    if (one) {
+      if (e.x != SKIP_NONE && e.y == code) {
+        L[0] = e.x;
+        R[0] = e.x + 1u;
+        pos += J;
+      } else {
+        dead = true;
+      }
+    }
+  }
+  Lq = L[0];
+  Rq = R[0];
+}
+
+/* SKIP (last template value, fused K <= 2 only): the walk with the skip table,
+ * launched when ix.skip is set; without it the kernel is the plain walk. */
+template <class G, int QPT, int MAXW, int SPLIT = 1, bool SKIP = false>
 __global__ __launch_bounds__(256) void task_kernel(IdxArgs ix, const uint32_t* __restrict__ qp,
                                                    const uint8_t* __restrict__ ascii, uint32_t m, uint64_t num,
                                                    uint32_t steps, uint32_t nwords, uint32_t* __restrict__ res)
@@ -203,6 +282,7 @@ __global__ __launch_bounds__(256) void task_kernel(IdxArgs ix, const uint32_t* _
   constexpr int SPW = G::SPW;
   constexpr int CW = MAXW > 0 ? (G::K == 3 ? k3_words<(MAXW > 0 ? MAXW : 1)>() : MAXW) : 1;
   static_assert(MAXW == 0 || QPT == 1, "fused packing: one query per thread");
+  static_assert(!SKIP || (MAXW > 0 && G::K <= 2), "skip table: fused task kernels at K <= 2");
   const uint64_t base = (uint64_t) blockIdx.x * (256 * QPT) + threadIdx.x;
   uint32_t cw[QPT][CW];
   uint32_t rc = 0;
@@ -246,6 +326,11 @@ __global__ __launch_bounds__(256) void task_kernel(IdxArgs ix, const uint32_t* _
       L[i] = lr.x;
       R[i] = lr.y;
     }
+  }
+  if constexpr (SKIP) {
+    skip_walk<G, MAXW, SPLIT>(ix, cw[0], steps, skip, L[0], R[0]);
+    *reinterpret_cast<uint2*>(res + 2 * base) = make_uint2(L[0], R[0]);
+    return;
   }
   for (uint32_t w = 0; w < nwords; ++w) {
     uint32_t word[QPT];
@@ -329,6 +414,40 @@ __global__ __launch_bounds__(256) void ftab_level_kernel(IdxArgs ix, uint32_t t,
       const uint32_t R = lf_stream<G>(ix, lr.y, c, sx);
       out[v | ((uint64_t) c << (2 * G::K * t))] = make_uint2(L, R);
     }
+  }
+}
+
+/* Skip table, level 0 (DESIGN.md 5a'): entry i = one K-step from the one-row
+ * interval [i, i+1) with row i's own K-mer code c -- the only code that can
+ * keep the interval non-empty -- taken on both ends by lf_stream, the search's
+ * own step (as ftab_level_kernel takes it), so every backend's semantics,
+ * lf_cap and the padding entries carry over; lf_row would take the
+ * AltCounters correction off, which the search keeps.  The entry {L', c} is
+ * valid iff the result is one row again (R' == L' + 1), i is no '$' row D_s
+ * (its K-mer holds the '$': no read code matches it) and L' is a table row.
+ *
+ * Exactness: skip_double_kernel composes two valid entries into one of twice
+ * the steps, {in[in[i].row].row, in[i].code | in[in[i].row].code << bits},
+ * and leaves it invalid when either half is.  By induction on the level every
+ * valid entry is exactly the composition of that many search steps from
+ * [i, i+1), each on a one-row interval, with the codes it records; a search
+ * that finds its next code bits equal to the entry's takes those same steps,
+ * so the jump changes no result.  A read whose bits differ does not use the
+ * entry at all. */
+template <class G>
+__global__ __launch_bounds__(256) void skip_level0_kernel(IdxArgs ix, uint64_t rows, uint2* __restrict__ out)
+{
+  for (uint64_t i = (uint64_t) blockIdx.x * 256 + threadIdx.x; i < rows; i += (uint64_t) gridDim.x * 256) {
+    const uint32_t X = (uint32_t) i;
+    const uint32_t c = row_code<G>(ix, X);
+    uint32_t sx[2 * G::K];
+    plane_xor<G::K>(c, sx);
+    const uint32_t L = lf_stream<G>(ix, X, c, sx);
+    const uint32_t R = lf_stream<G>(ix, X + 1u, c, sx);
+    bool ok = R == L + 1u && (uint64_t) L < rows;
+#pragma unroll
+    for (int s = 0; s < G::K; ++s) ok = ok && ix.dl.dpos[s] != X;
+    out[i] = ok ? make_uint2(L, c) : make_uint2(SKIP_NONE, 0u);
   }
 }
 
@@ -567,6 +686,8 @@ struct SearchLaunch {
   uint64_t ftab_n;
   /* remainder table build: rem bases -> ftab_out */
   uint32_t rem;
+  /* skip table, level 0 (Op::Skip0): num rows -> skip_out */
+  uint2* skip_out;
   /* index derivation: 2K-mer code per row (num rows), the rows of suffixes K..2K-1 */
   uint8_t* derive_codes;
   uint32_t* derive_isa;
@@ -581,6 +702,18 @@ static void launch_task_split(const SearchLaunch& a)
   if (a.maxw) {
     const uint64_t blocks = (a.num + 255) / 256;
     const size_t lds = 4 * (size_t) stage_slot_bytes(a.m);
+    if constexpr (G::K <= 2) {
+      if (a.ix.skip) {   /* the walk with the skip table; LDS: the staging, then 64 x maxw code words per wave */
+        const size_t lds_skip = std::max(lds, (size_t) 4 * 64 * 4 * (size_t) a.maxw);
+        if (a.maxw == 8)
+          hipLaunchKernelGGL((task_kernel<G, 1, 8, SPLIT, true>), dim3((uint32_t) blocks), dim3(256), lds_skip, a.st,
+                             a.ix, a.qp, a.ascii, a.m, a.num, a.steps, a.nwords, a.res);
+        else
+          hipLaunchKernelGGL((task_kernel<G, 1, 16, SPLIT, true>), dim3((uint32_t) blocks), dim3(256), lds_skip, a.st,
+                             a.ix, a.qp, a.ascii, a.m, a.num, a.steps, a.nwords, a.res);
+        return;
+      }
+    }
     if (a.maxw == 8)
       hipLaunchKernelGGL((task_kernel<G, 1, 8, SPLIT>), dim3((uint32_t) blocks), dim3(256), lds, a.st, a.ix, a.qp,
                          a.ascii, a.m, a.num, a.steps, a.nwords, a.res);
@@ -692,6 +825,17 @@ static hipError_t launch_rem_tab(const SearchLaunch& a)
 }
 
 template <class G>
+static hipError_t launch_skip0(const SearchLaunch& a)
+{
+  if constexpr (G::K <= 2 && G::LAY != LAY_GRP) {
+    hipLaunchKernelGGL((skip_level0_kernel<G>), dim3(grid_blocks((a.num + 255) / 256, 1u << 20)), dim3(256), 0, a.st,
+                       a.ix, a.num, a.skip_out);
+    return hipGetLastError();
+  }
+  return hipErrorInvalidValue;
+}
+
+template <class G>
 static hipError_t launch_count_lines(const SearchLaunch& a, unsigned long long* d_out)
 {
   const uint64_t blocks = (a.num + 255) / 256;
@@ -719,7 +863,7 @@ static hipError_t launch_perm(const SearchLaunch& a)
   return hipGetLastError();
 }
 
-enum class Op { Task, Coop, Count, Locate, Ftab, RemTab, CountLines, Derive, PermCheck };
+enum class Op { Task, Coop, Count, Locate, Ftab, RemTab, CountLines, Derive, PermCheck, Skip0 };
 
 /* Defined here, instantiated once per (K, NB, LAY) in kfmi_inst_*.hip. */
 template <int K, int NB, int LAY>
@@ -735,6 +879,7 @@ hipError_t dispatch_one(Op op, const SearchLaunch& a, unsigned long long* d_tota
     case Op::CountLines: return launch_count_lines<G>(a, d_total);
     case Op::Derive: return launch_derive<G>(a);
     case Op::PermCheck: return launch_perm<G>(a);
+    case Op::Skip0: return launch_skip0<G>(a);
     default: return launch_count<G>(a, d_total);
   }
 }

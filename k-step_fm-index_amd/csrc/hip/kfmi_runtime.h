@@ -55,6 +55,11 @@ struct kfmi_dev_index {
   /* bases of the auto table (KFMI_FTAB_AUTO), decided once per device copy
    * under ftab_mu (auto_ftab): -1 not yet, 0 none */
   int ftab_auto = -1;
+  /* skip table (DESIGN.md 5a'): one {row, code} entry per BWT row, K <= 2, task
+   * backends; same lifetime rule and mutex as the ftabs.  skip_auto: the auto
+   * decision of this copy (auto_skip): -1 not yet, 0 none, 1 built */
+  uint2* skip = nullptr;
+  int skip_auto = -1;
   /* remainder tables: [L, R) of every r-base read suffix, r = m % K in 1..3
    * (same lifetime rule as the ftabs, same mutex) */
   uint2* rtab[4] = {};
@@ -126,6 +131,7 @@ extern thread_local int t_device;
 extern thread_local int32_t t_last_error;
 extern thread_local double t_ms[3];   /* kfmi_last_timing: total, pack, lf (ms) */
 uint32_t ftab_bases(void);
+uint32_t skip_wanted(void);   /* 0 off, 1 on, 2 auto and in effect (the ftab setting is auto too) */
 
 /* backends and kernel dispatch (kfmi_search.hip) */
 bool is_coop(int backend);
@@ -141,6 +147,11 @@ int32_t use_ftab(kfmi_dev_index* di, hipStream_t st, IdxArgs& ix, uint32_t bases
 int32_t auto_ftab(kfmi_dev_index* di, hipStream_t st, uint32_t* bases);
 /* frees the tables of a device copy about to be replaced (handle locked exclusively) */
 void drop_ftabs(kfmi_dev_index* di);
+/* the skip table: the auto one, decided and built once per device copy (never
+ * an error when it does not fit), and ix.skip for a search under `want` =
+ * the caller's skip_wanted() */
+int32_t auto_skip(kfmi_dev_index* di, hipStream_t st);
+int32_t use_skip(kfmi_dev_index* di, hipStream_t st, IdxArgs& ix, uint32_t want);
 /* reads with m % K = rem != 0: layouts that take the remainder
  * table, and the table of an index (built on first use; clears the ftab) */
 bool rem_supported(int layout);
@@ -163,7 +174,7 @@ hipError_t h2d(void* dst, const void* src, uint64_t bytes, hipStream_t st);
 
 /* one device batch: queue pack + LF bracketed by ev[0..2], then wait (kfmi_search.hip) */
 int32_t search_enqueue(kfmi_dev_index* di, kfmi_dev_queries* dq, uint32_t* d_res, hipStream_t st, hipEvent_t* ev,
-                       uint32_t ftab);
+                       uint32_t ftab, uint32_t skip);
 int32_t search_finish(hipStream_t st, hipEvent_t* ev, double* ms);
 
 /* host memory helpers (kfmi_stream.hip) */

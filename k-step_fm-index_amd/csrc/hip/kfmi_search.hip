@@ -43,6 +43,7 @@ thread_local int t_device = -1;
 thread_local int32_t t_last_error = KFMI_SUCCESS;
 thread_local double t_ms[3] = {0, 0, 0};
 static thread_local int t_ftab = -1;   /* ftab bases; -1: KFMI_FTAB, else auto; -2: auto (kfmi_set_ftab) */
+static thread_local int t_skip = -1;   /* skip table; -1: KFMI_SKIP, else auto; 0 off, 1 on, 2: auto (kfmi_set_skip) */
 
 static int backend_from_name(const char* n)
 {
@@ -169,6 +170,42 @@ extern "C" uint32_t kfmi_ftab_auto_bases(uint64_t rows, uint32_t K, uint64_t bud
   while (n && (1ull << (2 * n)) > 2 * rows) n -= K;
   while (n && (8ull << (2 * n)) > budget_bytes) n -= K;
   return n;
+}
+
+extern "C" int32_t kfmi_set_skip(uint32_t mode)
+{
+  if (mode > 1 && mode != KFMI_SKIP_AUTO) return KFMI_E_BAD_ARGUMENT;
+  t_skip = mode == KFMI_SKIP_AUTO ? 2 : (int) mode;
+  return KFMI_SUCCESS;
+}
+
+/* The calling thread's skip-table setting resolved against its ftab setting
+ * (kstep_fmi.h): 0 = off, 1 = on (kfmi_set_skip(1) / KFMI_SKIP=1: built at the
+ * first search, an allocation failure is an error), 2 = auto and in effect --
+ * exactly when the ftab setting is auto as well, so an explicit kfmi_set_ftab
+ * (0 or N) keeps naming the walk it always named. */
+uint32_t skip_wanted(void)
+{
+  int v = t_skip;
+  if (v < 0) {
+    static const int env = [] {   /* KFMI_SKIP, read once per process */
+      const char* e = getenv("KFMI_SKIP");
+      if (!e || !*e || !strcmp(e, "auto")) return 2;
+      return atoi(e) ? 1 : 0;
+    }();
+    v = env;
+  }
+  if (v == 2) return ftab_bases() == KFMI_FTAB_AUTO ? 2u : 0u;
+  return (uint32_t) v;
+}
+
+extern "C" uint32_t kfmi_skip_in_effect(void) { return skip_wanted(); }
+
+/* The auto rule (kstep_fmi.h): host arithmetic only, so a CPU test calls it. */
+extern "C" uint32_t kfmi_skip_auto(uint64_t rows, uint32_t K, uint64_t budget_bytes)
+{
+  if (K < 1 || K > 2 || rows < 8 || rows > 0xFFFFFFFFull) return 0;
+  return 16 * rows <= budget_bytes ? 1u : 0u;
 }
 
 static std::atomic<uint64_t> g_ftab_budget{KFMI_FTAB_BUDGET_FREE};
@@ -759,6 +796,7 @@ void free_dev_index(kfmi_dev_index* di)
   if (di->ac_tail) (void) hipFree(di->ac_tail);
   for (uint2* t : di->ftab)
     if (t) (void) hipFree(t);
+  if (di->skip) (void) hipFree(di->skip);
   for (uint2* t : di->rtab)
     if (t) (void) hipFree(t);
   delete di;
@@ -1117,6 +1155,10 @@ IdxArgs idx_args(const kfmi_dev_index* di)
                            ? ((di->bwtsize + d - 1) / d + 2) * d - 1
                            : ((uint64_t) di->nentries + 1) * d - 1;
   ix.lf_cap = (uint32_t) std::min<uint64_t>(cap, 0xFFFFFFFFull);
+  ix.skip = nullptr;
+  ix.skip_rows = 0;
+  ix.skip_steps = 0;
+  ix.skip_split = 1;
   return ix;
 }
 
@@ -1515,6 +1557,134 @@ int32_t auto_ftab(kfmi_dev_index* di, hipStream_t st, uint32_t* bases)
   return KFMI_SUCCESS;
 }
 
+/* Skip table, doubling (the exactness argument: skip_level0_kernel): entry i of
+ * 2s steps = entry i of s steps, then the entry of the row it ends in, whose
+ * codes go `shift` = 2K*s bits above the first half's; invalid when either
+ * half is.  The second lookup is a gather into a table that can lie past the
+ * translation reach (24 GB at 3 Gbase): with `split` it is issued as four
+ * exec-masked 16-lane groups, like the task kernels' index gathers.  Entry
+ * loads are 8 bytes at 8-byte alignment, never wider (load_words' rule). */
+__global__ __launch_bounds__(256) void skip_double_kernel(const uint2* __restrict__ in, uint64_t rows, uint32_t shift,
+                                                          uint32_t split, uint2* __restrict__ out)
+{
+  const int grp = (int) (threadIdx.x & 63) / 16;
+  for (uint64_t i = (uint64_t) blockIdx.x * 256 + threadIdx.x; i < rows; i += (uint64_t) gridDim.x * 256) {
+    const uint2 a = in[i];
+    const bool ok = a.x != SKIP_NONE && (uint64_t) a.x < rows;
+    uint2 b = make_uint2(SKIP_NONE, 0u);
+    if (split) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+        if (ok && grp == g) b = in[a.x];
+    } else if (ok) {
+      b = in[a.x];
+    }
+    out[i] = (ok && b.x != SKIP_NONE) ? make_uint2(b.x, a.y | (b.y << shift)) : make_uint2(SKIP_NONE, 0u);
+  }
+}
+
+/* The skip table of a device copy built into di->skip (caller holds ftab_mu):
+ * level 0 from the uploaded layout, then log2(16 / K) doublings between two
+ * buffers; the second buffer is freed before returning.  KFMI_E_DEVICE_ALLOC
+ * when the two buffers do not fit. */
+static int32_t build_skip(kfmi_dev_index* di, hipStream_t st)
+{
+  const uint64_t rows = di->bwtsize;
+  uint2* buf[2] = {nullptr, nullptr};
+  for (uint2*& b : buf)
+    if (hipMalloc((void**) &b, 8ull * rows) != hipSuccess) {
+      (void) hipGetLastError();
+      if (buf[0]) (void) hipFree(buf[0]);
+      return KFMI_E_DEVICE_ALLOC;
+    }
+  SearchLaunch a{};
+  a.st = st;
+  a.ix = idx_args(di);
+  a.num = rows;
+  a.skip_out = buf[0];
+  bool ok = dispatch(Op::Skip0, di->K, di->nb, di->layout, a) == hipSuccess;
+  const uint32_t J = 16u / di->K;
+  const uint32_t split = split_for(8ull * rows, LAY_INTER) == 4u ? 1u : 0u;
+  int cur = 0;
+  for (uint32_t s = 1; ok && s < J; s *= 2, cur ^= 1) {
+    hipLaunchKernelGGL(skip_double_kernel, dim3(grid_blocks((rows + 255) / 256, 1u << 20)), dim3(256), 0, st, buf[cur],
+                       rows, 2u * di->K * s, split, buf[cur ^ 1]);
+    ok = hipGetLastError() == hipSuccess;
+  }
+  ok = hipStreamSynchronize(st) == hipSuccess && ok;
+  (void) hipFree(buf[cur ^ 1]);
+  if (!ok) {
+    (void) hipFree(buf[cur]);
+    return KFMI_E_KERNEL;
+  }
+  di->skip = buf[cur];   /* published complete; never replaced */
+  return KFMI_SUCCESS;
+}
+
+/* Whether a device copy takes the skip table at all: the per-lane (task)
+ * kernels at K <= 2.  The coop kernels, K = 3 / 4 and every non-search kernel
+ * ignore it (DESIGN.md 5a'), so no table is built for them. */
+static bool skip_applies(const kfmi_dev_index* di)
+{
+  return di->K >= 1 && di->K <= 2 && !is_coop(di->backend) && di->layout != LAY_GRP;
+}
+
+/* The auto skip table of an index, decided once per device copy after its auto
+ * ftab: built when kfmi_skip_auto says the table and its transient twin fit the
+ * budget -- a quarter of the device memory free right now, or
+ * kfmi_set_ftab_budget's bytes.  Never an error: without the table the search
+ * walks every K-step. */
+int32_t auto_skip(kfmi_dev_index* di, hipStream_t st)
+{
+  std::lock_guard<std::mutex> lk(di->ftab_mu);
+  if (di->skip_auto >= 0 || di->skip) return KFMI_SUCCESS;
+  di->skip_auto = 0;
+  if (!skip_applies(di)) return KFMI_SUCCESS;
+  uint64_t budget = g_ftab_budget.load(std::memory_order_relaxed);
+  if (budget == KFMI_FTAB_BUDGET_FREE) {
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
+      (void) hipGetLastError();
+      free_b = 0;
+    }
+    budget = (uint64_t) free_b / 4;
+  }
+  if (!kfmi_skip_auto(di->bwtsize, di->K, budget)) return KFMI_SUCCESS;
+  const int32_t e = build_skip(di, st);
+  if (e && e != KFMI_E_DEVICE_ALLOC) return e;
+  di->skip_auto = e ? 0 : 1;
+  return KFMI_SUCCESS;
+}
+
+/* Sets ix.skip for a search under the caller's resolved setting (skip_wanted):
+ * 2 = the auto table if this copy has one (decided here for a copy uploaded
+ * under another setting), 1 = built now if it is not there. */
+int32_t use_skip(kfmi_dev_index* di, hipStream_t st, IdxArgs& ix, uint32_t want)
+{
+  ix.skip = nullptr;
+  ix.skip_rows = 0;
+  ix.skip_steps = 0;
+  ix.skip_split = 1;
+  if (!want || !skip_applies(di)) return KFMI_SUCCESS;
+  if (want == 2) {
+    const int32_t e = auto_skip(di, st);
+    if (e) return e;
+  }
+  {
+    std::lock_guard<std::mutex> lk(di->ftab_mu);
+    if (!di->skip) {
+      if (want == 2) return KFMI_SUCCESS;
+      const int32_t e = build_skip(di, st);
+      if (e) return e;
+    }
+  }
+  ix.skip = di->skip;
+  ix.skip_rows = di->bwtsize;
+  ix.skip_steps = 16u / di->K;
+  ix.skip_split = split_for(8ull * di->bwtsize, LAY_INTER);
+  return KFMI_SUCCESS;
+}
+
 /* Frees the jump-start tables of a device copy that is about to be replaced
  * (caller holds the handle's exclusive lock: no search reads them).  They are
  * derived data, up to 34 GB each, and the replacing upload needs the memory:
@@ -1532,6 +1702,9 @@ void drop_ftabs(kfmi_dev_index* di)
       t = nullptr;
     }
   di->ftab_auto = -1;
+  if (di->skip) (void) hipFree(di->skip);   /* the skip table goes with them */
+  di->skip = nullptr;
+  di->skip_auto = -1;
 }
 
 /* The ftab of `bases` bases (KFMI_FTAB_AUTO: the index's auto table), built
@@ -1781,6 +1954,7 @@ extern "C" int32_t transferCPUtoGPU(void* index, void* queries, void* results)
         err = upload_index(f, backend, dev, ctx);
         /* the auto jump-start table is part of the upload, like the re-layout */
         if (!err && ftab_bases() == KFMI_FTAB_AUTO) err = auto_ftab(f->dev, ctx->st, nullptr);
+        if (!err && skip_wanted() == 2u) err = auto_skip(f->dev, ctx->st);   /* and the skip table after it */
         if (err) return err;
       }
       qk = device_steps(f);
@@ -1825,7 +1999,7 @@ extern "C" int32_t transferCPUtoGPU(void* index, void* queries, void* results)
 /* Queues pack (if not fused) + LF of one device batch on `st`, bracketed by
  * ev[0..2]; search_finish waits and reads the timings. */
 int32_t search_enqueue(kfmi_dev_index* di, kfmi_dev_queries* dq, uint32_t* d_res, hipStream_t st,
-                              hipEvent_t* ev, uint32_t ftab)
+                              hipEvent_t* ev, uint32_t ftab, uint32_t skip)
 {
   if (dq->device != di->device || dq->K != di->K) return KFMI_E_BAD_ARGUMENT;
   SearchLaunch a{};
@@ -1833,6 +2007,7 @@ int32_t search_enqueue(kfmi_dev_index* di, kfmi_dev_queries* dq, uint32_t* d_res
   a.ix = idx_args(di);
   int32_t err = use_ftab(di, st, a.ix, ftab);
   if (!err) err = use_rtab(di, st, a.ix, dq->rem);
+  if (!err) err = use_skip(di, st, a.ix, skip);
   if (err) return err;
   a.qp = dq->packed;
   a.ascii = dq->ascii;
@@ -1883,7 +2058,7 @@ extern "C" int32_t kfmi_search(void* index, void* queries, void* results)
   hipEvent_t* ev = err ? nullptr : thread_events(di->device);
   hipStream_t st = err ? nullptr : thread_stream(di->device);
   if (!err && (!ev || !st)) err = KFMI_E_NO_DEVICE;
-  if (!err) err = search_enqueue(di, q->dev, r->d_results, st, ev, ftab_bases());
+  if (!err) err = search_enqueue(di, q->dev, r->d_results, st, ev, ftab_bases(), skip_wanted());
   if (!err) err = search_finish(st, ev, t_ms);
   return err;
 }
@@ -2067,6 +2242,47 @@ static uint64_t ftab_bytes_of(kfmi_dev_index* di)
   for (uint32_t n = 1; n <= 16; ++n)
     if (di->ftab[n]) b += 8ull << (2 * n);
   return b;
+}
+
+static uint64_t skip_bytes_of(kfmi_dev_index* di)
+{
+  std::lock_guard<std::mutex> lk(di->ftab_mu);
+  return di->skip ? 8ull * di->bwtsize : 0ull;
+}
+
+extern "C" uint64_t kfmi_device_skip_bytes(void* index)
+{
+  kfmi_fmi_t* f = (kfmi_fmi_t*) index;
+  if (!f) return 0;
+  std::shared_lock<RwLock> lk(index_lock(f));
+  uint64_t b = 0;
+  if (f->grp) {
+    const GroupIndex* g = (const GroupIndex*) f->grp;
+    for (int i = 0; i < g->n; ++i) b += skip_bytes_of(g->di[i]);
+  } else if (f->dev) {
+    b = skip_bytes_of(f->dev);
+  }
+  return b;
+}
+
+/* Test accessor: the single-device copy's skip table copied to `out`
+ * (`entries` uint2 {row, code}); KFMI_E_NOT_ON_DEVICE without a table,
+ * KFMI_E_BAD_ARGUMENT when `entries` is not its row count. */
+extern "C" int32_t kfmi_device_skip_table(void* index, void* out, uint64_t entries, uint32_t* steps)
+{
+  kfmi_fmi_t* f = (kfmi_fmi_t*) index;
+  if (!f || !out) return KFMI_E_BAD_ARGUMENT;
+  DeviceGuard dg;
+  std::shared_lock<RwLock> lk(index_lock(f));
+  kfmi_dev_index* di = f->dev;
+  if (!di) return KFMI_E_NOT_ON_DEVICE;
+  std::lock_guard<std::mutex> tl(di->ftab_mu);
+  if (!di->skip) return KFMI_E_NOT_ON_DEVICE;
+  if (entries != di->bwtsize) return KFMI_E_BAD_ARGUMENT;
+  if (hipSetDevice(di->device) != hipSuccess) return KFMI_E_NO_DEVICE;
+  HIP_OK(hipMemcpy(out, di->skip, 8ull * entries, hipMemcpyDeviceToHost));
+  if (steps) *steps = 16u / di->K;
+  return KFMI_SUCCESS;
 }
 
 extern "C" uint64_t kfmi_device_ftab_bytes(void* index)

@@ -339,7 +339,8 @@ extern "C" int32_t kfmi_stream_release(void)
  * slice of a device group).  ms3 = {wall, host packing/staging, blocked on
  * the GPU}; *npacked = reads sent as host-packed words. */
 static int32_t stream_on(kfmi_dev_index* di, int member, const char* ascii, uint64_t num, uint32_t size,
-                         uint32_t* results, uint64_t chunk, uint32_t ftab, double* ms3, uint64_t* npacked_out)
+                         uint32_t* results, uint64_t chunk, uint32_t ftab, uint32_t skip, double* ms3,
+                         uint64_t* npacked_out)
 {
   const uint32_t K = di->K;
   DevCtx* ctx = nullptr;
@@ -404,6 +405,7 @@ static int32_t stream_on(kfmi_dev_index* di, int member, const char* ascii, uint
   IdxArgs ix = idx_args(di);
   err = use_ftab(di, ctx->st, ix, ftab);   /* the caller's setting (member threads have their own) */
   if (!err) err = use_rtab(di, ctx->st, ix, rem);   /* rem != 0: the table, no ftab (as kfmi_search) */
+  if (!err) err = use_skip(di, ctx->st, ix, skip);
   if (err) return err;
   int32_t status = KFMI_SUCCESS;
   using clk = std::chrono::steady_clock;
@@ -527,9 +529,9 @@ extern "C" int32_t kfmi_search_stream(void* index, const char* ascii, uint64_t n
   double ms[KFMI_MAX_GROUP][3] = {};
   uint64_t np[KFMI_MAX_GROUP] = {};
   int32_t err = KFMI_SUCCESS;
-  const uint32_t ftab = ftab_bases();
+  const uint32_t ftab = ftab_bases(), skip = skip_wanted();
   if (!g) {
-    err = stream_on(f->dev, 0, ascii, num, size, results, chunk, ftab, ms[0], &np[0]);
+    err = stream_on(f->dev, 0, ascii, num, size, results, chunk, ftab, skip, ms[0], &np[0]);
   } else {
     const int n = g->n;
     uint64_t per = (num + n - 1) / n;
@@ -540,7 +542,8 @@ extern "C" int32_t kfmi_search_stream(void* index, const char* ascii, uint64_t n
     for (int i = 0; i < n; ++i) {
       const uint64_t a = per * i < num ? per * i : num, b = per * (i + 1) < num ? per * (i + 1) : num;
       th.emplace_back([&, i, a, b] {
-        errs[i] = stream_on(g->di[i], i, ascii + a * size, b - a, size, results + 2 * a, chunk, ftab, ms[i], &np[i]);
+        errs[i] = stream_on(g->di[i], i, ascii + a * size, b - a, size, results + 2 * a, chunk, ftab, skip, ms[i],
+                              &np[i]);
       });
     }
     for (auto& t : th) t.join();

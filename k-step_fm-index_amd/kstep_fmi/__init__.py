@@ -121,6 +121,11 @@ def load() -> ctypes.CDLL:
         "kfmi_ftab_auto_bases": (u32, [u64, u32, u64]),
         "kfmi_set_ftab_budget": (i32, [u64]),
         "kfmi_device_ftab_bytes": (u64, [vp]),        "kfmi_set_split_class": (i32, [u32]),
+        "kfmi_set_skip": (i32, [u32]),
+        "kfmi_skip_in_effect": (u32, []),
+        "kfmi_skip_auto": (u32, [u64, u32, u64]),
+        "kfmi_device_skip_bytes": (u64, [vp]),
+        "kfmi_device_skip_table": (i32, [vp, vp, u64, ctypes.POINTER(u32)]),
         "kfmi_set_fused": (i32, [i32]),
         "kfmi_set_walk_check": (i32, [u32]),
         "kfmi_walk_check_last": (i32, []),
@@ -180,6 +185,28 @@ def set_ftab_budget(nbytes) -> None:
     """Byte budget of the auto rule (process-wide test knob); None = a quarter
     of the free device memory."""
     _check(load().kfmi_set_ftab_budget(0xFFFFFFFFFFFFFFFF if nbytes is None else int(nbytes)), "set_ftab_budget")
+
+
+SKIP_AUTO = 0xFFFFFFFF
+
+
+def set_skip(mode) -> None:
+    """Skip table: 0 = off, 1 = on, "auto" (the default) = in effect exactly
+    when the ftab setting is "auto" too; per calling thread."""
+    n = SKIP_AUTO if mode == "auto" else int(mode)
+    _check(load().kfmi_set_skip(n), f"set_skip({mode})")
+
+
+def skip_in_effect() -> int:
+    """The calling thread's skip setting resolved against its ftab setting:
+    0 = off, 1 = on (explicit), 2 = auto and in effect."""
+    return int(load().kfmi_skip_in_effect())
+
+
+def skip_auto(rows: int, k: int, budget_bytes: int) -> bool:
+    """The auto rule: whether an index of `rows` (n + 1) rows and K = k gets a
+    skip table within `budget_bytes`."""
+    return bool(load().kfmi_skip_auto(int(rows), int(k), int(budget_bytes)))
 
 
 def set_split_class(cls: int) -> None:
@@ -380,6 +407,19 @@ class Index(_Handle):
     def ftab_bytes(self) -> int:
         """Bytes of the jump-start tables beside the device copies (not in device_bytes)."""
         return int(load().kfmi_device_ftab_bytes(self._p))
+
+    def skip_bytes(self) -> int:
+        """Bytes of the skip tables beside the device copies (not in device_bytes / ftab_bytes)."""
+        return int(load().kfmi_device_skip_bytes(self._p))
+
+    def skip_table(self):
+        """Test accessor: (J, uint32 [rows, 2] of {row, code}) of the single-device copy's skip table."""
+        rows = int(self.header()["bwtsize"])
+        out = np.empty((rows, 2), dtype=np.uint32)
+        j = ctypes.c_uint32(0)
+        _check(load().kfmi_device_skip_table(self._p, out.ctypes.data_as(ctypes.c_void_p), rows, ctypes.byref(j)),
+               "skip_table")
+        return int(j.value), out
 
     def sa(self):
         """(rate, uint32 view of the row-sampled suffix array); (0, empty) when absent."""
