@@ -425,6 +425,71 @@ int32_t kfmi_stream_release(void);
  * on the host (the rest went over PCIe as ASCII). */
 double  kfmi_stream_hostpacked_fraction(void);
 
+/* ---- both strands (not in the reference, which searches a read as written) --
+ * A sequencing read comes from either strand of the genome.  With code =
+ * base2index(byte) (A0 C1 G2 T3), the reverse strand of a read P of m bases is
+ * the read P' with
+ *     P'[j] = "ACGT"[3 - base2index(P[m-1-j])].
+ * The definition is on codes: N and every other byte go the way base2index
+ * sends them (N -> G, lowercase like uppercase) and are complemented from
+ * there, so P' is always ACGT.  A reverse-strand interval is, bit for bit,
+ * what the forward search of the same backend returns for P' -- every backend
+ * and its semantics (AltCounters included), K = 1-4, any m (m % K != 0 through
+ * the remainder table; AltCounters layouts return 33 there, as the forward
+ * search does), jump-start table on or off.
+ *   strands = KFMI_STRAND_FWD is exactly kfmi_search / kfmi_search_stream /
+ * kfmi_search_cpu (the same code path).  KFMI_STRAND_REV: `results` holds num
+ * intervals, interval q that of P'_q.  KFMI_STRAND_BOTH: a results handle of
+ * 2 * num intervals (kfmi_results_alloc(2 * num), transferred as usual), or
+ * 4 * num u32 for the streamed call: interval 2q is the forward interval of
+ * read q, 2q + 1 its reverse one, so every slice of reads is a contiguous slice
+ * of results and kfmi_locate works on such a handle unchanged (it sees 2 * num
+ * intervals).  Any other `strands` value, or a results handle whose num does
+ * not fit, returns KFMI_E_BAD_ARGUMENT.  No environment variable and no
+ * per-thread setting select the strands: the result size differs, so every
+ * existing call stays as it is.
+ *   On the device the reverse strand's code words are derived from the forward
+ * reads already there: no second copy of the reads is made on
+ * the host, crosses PCIe or is kept in HBM as ASCII.  The task backends at
+ * K = 1, 2 pack either strand inside the search kernel (reads of up to 256
+ * bases with m % K == 0, ASCII on the device, fused packing on): one launch
+ * and no memory beyond the forward search's.  Every other case -- the coop
+ * backends, K = 3 / 4, m % K != 0, longer reads, KFMI_UPLOAD=packed handles
+ * and host-packed stream chunks -- first writes the code words of the ns * num
+ * tasks with a pack launch and runs the backend's forward LF kernel on them
+ * (with the skip table where it is in effect).  Those words take
+ * 8 * (ceil(m / 16) + 1) bytes per read of device memory (64 B at m = 100),
+ * allocated by the first such search of a queries handle and kept until
+ * freeQueriesGPU / a new transfer, and as much per read of a stream slot
+ * (freed by kfmi_stream_release).  They belong to the queries handle: two
+ * strand searches of ONE queries handle must not run at the same time (REV and
+ * BOTH lay the words out differently); searches of different handles, and
+ * forward searches, run concurrently as before.
+ *   Device groups: kfmi_search_stream_strands supports them (each member
+ * streams its slice of reads [a, b) into results + 2 * ns * a, ns = 1 or 2
+ * strands); kfmi_search_strands returns KFMI_E_NOT_IMPLEMENTED on group handles
+ * for strands != FWD (the group transfer cuts results by their own count,
+ * which is then not the read slices').
+ *   kfmi_search_cpu_strands is the host search of the same tasks (it writes the
+ * reverse complements to a temporary; the results handle may be larger than
+ * ns * num, as for kfmi_search_cpu).  kfmi_revcomp_queries writes P' of every
+ * read (num * size bytes at `out`, which must not overlap `ascii`), over the
+ * host workers like loadQueries. */
+enum { KFMI_STRAND_FWD = 1, KFMI_STRAND_REV = 2, KFMI_STRAND_BOTH = 3 };
+int32_t kfmi_search_strands(void *index, void *queries, void *results, uint32_t strands);
+int32_t kfmi_search_stream_strands(void *index, const char *ascii, uint64_t num, uint32_t size,
+                                   uint32_t *results, uint64_t chunk, uint32_t strands);
+int32_t kfmi_search_cpu_strands(void *index, void *queries, void *results, uint32_t strands, int32_t nthreads);
+int32_t kfmi_revcomp_queries(const char *ascii, uint64_t num, uint32_t size, char *out);   /* P -> P', host */
+/* Test accessor (host only, no device): the code words of the ns * num tasks of
+ * `strands` (REV or BOTH) from the forward code words of kfmi_pack_queries_k
+ * (k in {1, 2, 4}; rows x num in, rows x ns * num out), computed by the same
+ * code as the device kernel that serves KFMI_UPLOAD=packed handles and
+ * host-packed stream chunks.  A reverse task's column equals
+ * kfmi_pack_queries_k of kfmi_revcomp_queries of the read. */
+int32_t kfmi_strand_words_host(const uint32_t *words, uint64_t num, uint32_t size, uint32_t k,
+                               uint32_t strands, uint32_t *out);
+
 /* Diagnostic (not in the reference): replays the line requests a
  * task-mid / coop-mid search of `queries` makes (MID128 layout, K = 2, d = 64,
  * m % K == 0, both uploaded) without the LF chain's dependence: a trace launch

@@ -14,6 +14,7 @@
 
 #include "kfmi_device.h"
 #include "kfmi_grid.h"
+#include "kfmi_strands.h"
 #include "kfmi_coop.h"
 #include "kfmi_locate.h"
 
@@ -380,6 +381,106 @@ __global__ __launch_bounds__(256) void task_kernel(IdxArgs ix, const uint32_t* _
   }
 }
 
+/* Strand searches (kfmi_strands.hip): the walk with the skip
+ * table on code words a pack launch wrote -- the ns * num task columns of qp,
+ * word-major, 16 bases per word (K <= 2), at most MAXW words per task.  A lane
+ * loads its column (a word row is consecutive tasks: coalesced) where the fused
+ * kernel converts its ASCII row; the jump start, the remainder lookup and
+ * skip_walk are the fused kernel's.  The forward kernels are not touched. */
+template <class G, int MAXW, int SPLIT>
+__global__ __launch_bounds__(256) void task_words_skip_kernel(IdxArgs ix, const uint32_t* __restrict__ qp, uint64_t num,
+                                                              uint32_t steps, uint32_t nwords,
+                                                              uint32_t* __restrict__ res)
+{
+  static_assert(G::K <= 2 && MAXW > 0, "skip table: task kernels at K <= 2");
+  const uint64_t q = (uint64_t) blockIdx.x * 256 + threadIdx.x;
+  if (q >= num) return;
+  uint32_t cw[MAXW];
+#pragma unroll
+  for (int k = 0; k < MAXW; ++k) cw[k] = (uint32_t) k < nwords ? qp[(uint64_t) k * num + q] : 0u;
+  uint32_t L = 0, R = ix.bwtsize, skip = 0;
+  if (ix.ftab && steps >= ix.ftab_steps) {   /* wave-uniform: jump start from the ftab */
+    skip = ix.ftab_steps;
+    const uint2 lr = ix.ftab[cw[0] & ix.ftab_mask];
+    L = lr.x;
+    R = lr.y;
+  }
+  if (ix.rem) {   /* wave-uniform: m % K != 0, the last rem bases from the remainder table */
+    const uint2 lr = ix.rtab[qp[(uint64_t) nwords * num + q]];
+    L = lr.x;
+    R = lr.y;
+  }
+  skip_walk<G, MAXW, SPLIT>(ix, cw, steps, skip, L, R);
+  *reinterpret_cast<uint2*>(res + 2 * q) = make_uint2(L, R);
+}
+
+/* Strand-aware fused packing for a 256-thread block, one task
+ * per thread, m % K == 0: stage_query_codes for the ns * num tasks of
+ * `strands` (2 = the reverse strand, 3 = both: task 2q + strand).  In BOTH a
+ * wave's 64 lanes are 32 reads, so it stages half the rows per task, and lanes
+ * 2i and 2i + 1 convert the same LDS row; a wave's first read, 32 * (waves
+ * before it), keeps r0 * m % 16 == 0 for every m.  Every lane packs its row
+ * forward (row_codes), derives the reverse stream in registers
+ * (reverse_stream: fixed indices, a wave-uniform shift) and keeps one of the
+ * two under a per-lane select -- no divergent branch around two packers.
+ * LDS per wave: stage_slot_bytes(m).  Every thread of the block must call it. */
+template <int MAXW>
+__device__ __forceinline__ void stage_strand_codes(const uint8_t* __restrict__ ascii, uint64_t num, uint32_t m,
+                                                   uint8_t* __restrict__ lds, uint32_t (&cw)[MAXW], uint32_t strands)
+{
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  const uint32_t both = strands == 3u ? 1u : 0u;
+  const uint32_t rpr = stage_rows(m);
+  const uint32_t lr = lane >> both;                  /* the lane's read among its wave's 64 >> both */
+  const bool rev = both ? (lane & 1u) != 0u : true;
+  uint8_t* wl = lds + wv * stage_slot_bytes(m);
+  const uint64_t q0 = ((uint64_t) blockIdx.x * 256 + wv * 64) >> both;
+#pragma unroll 1
+  for (uint32_t h = 0; h < (64u >> both) / rpr; ++h) {
+    const uint64_t r0 = q0 + h * rpr;
+    const uint64_t nr = r0 < num ? (num - r0 < rpr ? num - r0 : rpr) : 0;
+    const uint32_t n16 = (uint32_t) ((nr * m + 15) / 16);           /* <= 15 bytes of slack read */
+    const uint4* src = reinterpret_cast<const uint4*>(ascii + r0 * m);   /* r0*m % 16 == 0 */
+    for (uint32_t i = lane; i < n16; i += 64) reinterpret_cast<uint4*>(wl)[i] = src[i];
+    __syncthreads();
+    if (lr / rpr == h) {
+      uint32_t fw[MAXW], rv[MAXW];
+      row_codes<MAXW>(wl, (uint64_t) (lr % rpr) * m, m, fw);
+      reverse_stream<MAXW>(fw, m, rv);
+#pragma unroll
+      for (int k = 0; k < MAXW; ++k) cw[k] = rev ? rv[k] : fw[k];
+    }
+    __syncthreads();
+  }
+}
+
+/* The fused task kernel of a strand search: ns * num tasks on the ASCII reads
+ * of num reads, K <= 2, m % K == 0, m <= 16 * MAXW.  Only the staging differs
+ * from task_kernel<G, 1, MAXW, SPLIT, true>: the jump start and skip_walk are
+ * the same (without a skip table skip_walk takes every K-step from the code
+ * words in LDS).  The forward kernels are not touched. */
+template <class G, int MAXW, int SPLIT>
+__global__ __launch_bounds__(256) void task_strands_kernel(IdxArgs ix, const uint8_t* __restrict__ ascii, uint32_t m,
+                                                           uint64_t num, uint32_t steps, uint32_t strands,
+                                                           uint32_t* __restrict__ res)
+{
+  static_assert(G::K <= 2 && MAXW > 0, "strand staging: task kernels at K <= 2");
+  extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
+  uint32_t cw[MAXW];
+  stage_strand_codes<MAXW>(ascii, num, m, stage, cw, strands);   /* whole block, before any exit */
+  const uint64_t t = (uint64_t) blockIdx.x * 256 + threadIdx.x;
+  if (t >= (strands == 3u ? 2u : 1u) * num) return;
+  uint32_t L = 0, R = ix.bwtsize, skip = 0;
+  if (ix.ftab && steps >= ix.ftab_steps) {   /* wave-uniform: jump start from the ftab */
+    skip = ix.ftab_steps;
+    const uint2 lr = ix.ftab[cw[0] & ix.ftab_mask];
+    L = lr.x;
+    R = lr.y;
+  }
+  skip_walk<G, MAXW, SPLIT>(ix, cw, steps, skip, L, R);
+  *reinterpret_cast<uint2*>(res + 2 * t) = make_uint2(L, R);
+}
+
 /* ftab construction: [L, R) of every code stream v of ftab_steps K-steps
  * (the search's own first steps, from [0, n+1)), each end by lf_stream --
  * the per-row step of every non-search kernel.  Round 5 detoured this build
@@ -668,6 +769,11 @@ struct SearchLaunch {
   const uint8_t* ascii;   /* fused packing: ASCII rows of m bases */
   uint32_t m;
   int maxw;               /* 0: packed words in qp; 8/16: fused packing */
+  int words_maxw;         /* strand searches, maxw == 0: 8/16 = the words in qp fit that many registers and
+                             the task backends walk them with the skip table when ix.skip is set
+                             (task_words_skip_kernel); 0 = the plain walk of the words, as every other caller */
+  uint32_t strands;       /* strand searches with fused packing (maxw != 0, task backends, K <= 2, m % K == 0):
+                             2 / 3 = num reads run as 1 / 2 tasks each (task_strands_kernel); 0 = forward */
   uint64_t num;
   uint32_t steps, nwords;
   uint32_t* res;
@@ -700,8 +806,21 @@ template <class G, int SPLIT>
 static void launch_task_split(const SearchLaunch& a)
 {
   if (a.maxw) {
-    const uint64_t blocks = (a.num + 255) / 256;
     const size_t lds = 4 * (size_t) stage_slot_bytes(a.m);
+    if constexpr (G::K <= 2) {
+      if (a.strands) {   /* strand-aware staging, then the fused kernel's own walk */
+        const uint64_t tblocks = ((a.strands == 3u ? 2u : 1u) * a.num + 255) / 256;
+        const size_t lds_str = std::max(lds, (size_t) 4 * 64 * 4 * (size_t) a.maxw);
+        if (a.maxw == 8)
+          hipLaunchKernelGGL((task_strands_kernel<G, 8, SPLIT>), dim3((uint32_t) tblocks), dim3(256), lds_str, a.st,
+                             a.ix, a.ascii, a.m, a.num, a.steps, a.strands, a.res);
+        else
+          hipLaunchKernelGGL((task_strands_kernel<G, 16, SPLIT>), dim3((uint32_t) tblocks), dim3(256), lds_str, a.st,
+                             a.ix, a.ascii, a.m, a.num, a.steps, a.strands, a.res);
+        return;
+      }
+    }
+    const uint64_t blocks = (a.num + 255) / 256;
     if constexpr (G::K <= 2) {
       if (a.ix.skip) {   /* the walk with the skip table; LDS: the staging, then 64 x maxw code words per wave */
         const size_t lds_skip = std::max(lds, (size_t) 4 * 64 * 4 * (size_t) a.maxw);
@@ -722,6 +841,18 @@ static void launch_task_split(const SearchLaunch& a)
                          a.ascii, a.m, a.num, a.steps, a.nwords, a.res);
   } else {
     const uint64_t blocks = (a.num + 255) / 256;
+    if constexpr (G::K <= 2) {
+      if (a.ix.skip && a.words_maxw) {   /* strand searches: the skip-table walk on packed words */
+        const size_t lds_skip = (size_t) 4 * 64 * 4 * (size_t) a.words_maxw;
+        if (a.words_maxw == 8)
+          hipLaunchKernelGGL((task_words_skip_kernel<G, 8, SPLIT>), dim3((uint32_t) blocks), dim3(256), lds_skip, a.st,
+                             a.ix, a.qp, a.num, a.steps, a.nwords, a.res);
+        else
+          hipLaunchKernelGGL((task_words_skip_kernel<G, 16, SPLIT>), dim3((uint32_t) blocks), dim3(256), lds_skip,
+                             a.st, a.ix, a.qp, a.num, a.steps, a.nwords, a.res);
+        return;
+      }
+    }
     hipLaunchKernelGGL((task_kernel<G, 1, 0, SPLIT>), dim3((uint32_t) blocks), dim3(256), 0, a.st, a.ix, a.qp,
                        a.ascii, a.m, a.num, a.steps, a.nwords, a.res);
   }
@@ -741,7 +872,9 @@ static hipError_t launch_task(const SearchLaunch& a)
       else launch_task_split<G, 7>(a);
       return hipGetLastError();
     }
-    if (want == 4 || (want == 2 && a.maxw == 8)) {
+    /* the words-skip kernel takes the fused skip kernel's form; the plain walk of words keeps its own */
+    const int mw = a.maxw ? a.maxw : (a.ix.skip ? a.words_maxw : 0);
+    if (want == 4 || (want == 2 && mw == 8)) {
       launch_task_split<G, 4>(a);
       return hipGetLastError();
     }

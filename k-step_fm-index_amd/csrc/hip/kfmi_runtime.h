@@ -78,6 +78,10 @@ struct kfmi_dev_queries {
    * by one remainder-table lookup before its K-steps (query_geometry) */
   uint32_t size = 0, K = 0, steps = 0, nwords = 0, rem = 0;
   uint32_t packed_rows = 0;    /* rows allocated in `packed` (>= nwords + 1) */
+  /* strand searches (kfmi_strands.hip): the code words of the ns * num tasks,
+   * (nwords + 1) rows; allocated by the first such search (strand_reserve) */
+  uint32_t* strand_words = nullptr;
+  uint64_t strand_cap = 0;     /* words allocated */
 };
 
 namespace kfmi {
@@ -176,6 +180,17 @@ hipError_t h2d(void* dst, const void* src, uint64_t bytes, hipStream_t st);
 int32_t search_enqueue(kfmi_dev_index* di, kfmi_dev_queries* dq, uint32_t* d_res, hipStream_t st, hipEvent_t* ev,
                        uint32_t ftab, uint32_t skip);
 int32_t search_finish(hipStream_t st, hipEvent_t* ev, double* ms);
+
+/* strand searches (kfmi_strands.hip): dq->strand_words sized for both strands
+ * of cq reads, and the launch that fills `out` with the task columns of
+ * `strands` (REV or BOTH) -- from dq->ascii, or from the forward code words in
+ * dq->packed when from_words (or when the device has no ASCII) */
+int32_t strand_reserve(kfmi_dev_queries* dq, uint64_t cq, DevCtx* ctx);
+int strand_words_maxw(uint32_t nwords);   /* SearchLaunch::words_maxw of a strand search */
+/* SearchLaunch::maxw of a strand search that packs in the task kernel (task_strands_kernel); 0 = the pack launch */
+int strand_fused_maxw(const kfmi_dev_index* di, bool ascii, uint32_t K, uint32_t steps, uint32_t rem);
+hipError_t launch_strand_pack(const kfmi_dev_queries* dq, uint32_t* out, uint32_t strands, bool from_words,
+                              hipStream_t st);
 
 /* host memory helpers (kfmi_stream.hip) */
 bool host_pinned(const void* p);

@@ -1740,6 +1740,7 @@ void free_dev_queries(kfmi_dev_queries* dq)
   if (dq->device >= 0) (void) hipSetDevice(dq->device);
   if (dq->ascii) (void) hipFree(dq->ascii);
   if (dq->packed) (void) hipFree(dq->packed);
+  if (dq->strand_words) (void) hipFree(dq->strand_words);
   delete dq;
 }
 

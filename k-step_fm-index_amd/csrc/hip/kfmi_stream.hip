@@ -63,6 +63,7 @@ struct StreamSlot {
   uint32_t* h_out = nullptr;
   uint32_t* h_pk = nullptr;    /* pinned host-packed code words */
   uint64_t cap_q = 0, cap_in = 0, cap_words = 0;
+  uint32_t cap_ns = 1;         /* strands d_res / h_out are sized for (2 * cap_ns u32 per read) */
   uint64_t q0 = 0, n = 0;
   bool busy = false;
 };
@@ -97,6 +98,7 @@ static void pool_free(int dev, int member)
     if (s.st) (void) hipStreamSynchronize(s.st);
     if (s.dq.ascii) (void) hipFree(s.dq.ascii);
     if (s.dq.packed) (void) hipFree(s.dq.packed);
+    if (s.dq.strand_words) (void) hipFree(s.dq.strand_words);
     if (s.d_res) (void) hipFree(s.d_res);
     if (s.h_in) (void) hipHostFree(s.h_in);
     if (s.h_out) (void) hipHostFree(s.h_out);
@@ -110,9 +112,10 @@ static void pool_free(int dev, int member)
   p.init = false;
 }
 
-/* Grows slot buffers to hold `cq` queries of `size` bytes packed in `words` words. */
+/* Grows slot buffers to hold `cq` queries of `size` bytes packed in `words` words,
+ * and the results of their `ns` strands (2 * ns u32 per read). */
 static int32_t slot_reserve(StreamSlot& s, uint64_t cq, uint32_t size, uint32_t words, bool stage_in, bool stage_out,
-                     bool host_pack)
+                     bool host_pack, uint32_t ns)
 {
   if (!s.st) {
     if (hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking) != hipSuccess ||
@@ -131,7 +134,7 @@ static int32_t slot_reserve(StreamSlot& s, uint64_t cq, uint32_t size, uint32_t 
   }
   if (stage_in && !s.h_in && hipHostMalloc((void**) &s.h_in, s.cap_in, hipHostMallocDefault) != hipSuccess)
     return KFMI_E_ALLOCATING_MFASTA;
-  if (cq > s.cap_q || (uint64_t) words * cq > s.cap_words) {
+  if (cq > s.cap_q || (uint64_t) words * cq > s.cap_words || ns > s.cap_ns) {
     if (s.dq.packed) (void) hipFree(s.dq.packed);
     if (s.d_res) (void) hipFree(s.d_res);
     if (s.h_out) { (void) hipHostFree(s.h_out); s.h_out = nullptr; }
@@ -139,13 +142,15 @@ static int32_t slot_reserve(StreamSlot& s, uint64_t cq, uint32_t size, uint32_t 
     s.dq.packed = nullptr;
     s.d_res = nullptr;
     s.cap_q = s.cap_words = 0;
+    s.cap_ns = 1;
     if (hipMalloc((void**) &s.dq.packed, 4ull * words * cq) != hipSuccess ||
-        hipMalloc((void**) &s.d_res, 8ull * cq) != hipSuccess)
+        hipMalloc((void**) &s.d_res, 8ull * ns * cq) != hipSuccess)
       return KFMI_E_DEVICE_ALLOC;
+    s.cap_ns = ns;
     s.cap_q = cq;
     s.cap_words = (uint64_t) words * cq;
   }
-  if (stage_out && !s.h_out && hipHostMalloc((void**) &s.h_out, 8ull * s.cap_q, hipHostMallocDefault) != hipSuccess)
+  if (stage_out && !s.h_out && hipHostMalloc((void**) &s.h_out, 8ull * s.cap_ns * s.cap_q, hipHostMallocDefault) != hipSuccess)
     return KFMI_E_ALLOCATING_RESULTS;
   if (host_pack && !s.h_pk && hipHostMalloc((void**) &s.h_pk, 4ull * s.cap_words, hipHostMallocDefault) != hipSuccess)
     return KFMI_E_ALLOCATING_MFASTA;
@@ -340,8 +345,12 @@ extern "C" int32_t kfmi_stream_release(void)
  * the GPU}; *npacked = reads sent as host-packed words. */
 static int32_t stream_on(kfmi_dev_index* di, int member, const char* ascii, uint64_t num, uint32_t size,
                          uint32_t* results, uint64_t chunk, uint32_t ftab, uint32_t skip, double* ms3,
-                         uint64_t* npacked_out)
+                         uint64_t* npacked_out, uint32_t strands = KFMI_STRAND_FWD)
 {
+  /* strands != FWD: ns intervals per read (task 2q + strand in BOTH); a chunk's
+   * upload is the forward one, its task columns are written on the device */
+  const bool stranded = strands != KFMI_STRAND_FWD;
+  const uint32_t ns = strands == KFMI_STRAND_BOTH ? 2u : 1u;
   const uint32_t K = di->K;
   DevCtx* ctx = nullptr;
   int32_t err = ctx_for(di->device, &ctx);
@@ -388,7 +397,12 @@ static int32_t stream_on(kfmi_dev_index* di, int member, const char* ascii, uint
   const int nslot = stream_slots();
   for (int k = 0; k < nslot; ++k) {
     StreamSlot& s = pool.slot[k];
-    err = slot_reserve(s, chunk, size, rows, !pin_in && any_ascii, !pin_out, any_pack);
+    err = slot_reserve(s, chunk, size, rows, !pin_in && any_ascii, !pin_out, any_pack, ns);
+    /* task columns: for host-packed chunks, and for ASCII ones the task kernel does not pack itself */
+    if (!err && stranded && (any_pack || !strand_fused_maxw(di, true, K, steps, rem))) {
+      s.dq.nwords = nwords;
+      err = strand_reserve(&s.dq, chunk, ctx);
+    }
     if (err) return err;
     s.busy = false;
   }
@@ -418,7 +432,7 @@ static int32_t stream_on(kfmi_dev_index* di, int member, const char* ascii, uint
     wait_ms += since(tw);
     if (!ok) status = KFMI_E_KERNEL;
     else {
-      if (!pin_out) par_copy(results + 2 * s.q0, s.h_out, 8ull * s.n);
+      if (!pin_out) par_copy(results + 2 * ns * s.q0, s.h_out, 8ull * ns * s.n);
       float x = 0;
       if (hipEventElapsedTime(&x, s.x0, s.x1) == hipSuccess && s.n && x > 0) {
         if (s.packed_mode) keep_min(pool.r_xp, x / (s.n * pbytes));
@@ -474,23 +488,30 @@ static int32_t stream_on(kfmi_dev_index* di, int member, const char* ascii, uint
     SearchLaunch a;
     a.st = s.st;
     a.ix = ix;
-    a.qp = s.dq.packed;
+    a.qp = stranded ? s.dq.strand_words : s.dq.packed;
     a.ascii = s.dq.ascii;
     a.m = size;
-    a.maxw = host_pack ? 0 : fused_maxw(di->backend, K * steps);
-    a.num = s.n;
+    /* an ASCII chunk of a strand search packs in the task kernel where that kernel exists
+     * (strand_fused_maxw), like a forward one; else its task columns are written first */
+    a.maxw = host_pack ? 0
+                       : (stranded ? strand_fused_maxw(di, true, K, steps, rem) : fused_maxw(di->backend, K * steps));
+    const bool str_pack = stranded && !a.maxw;
+    a.strands = stranded && a.maxw ? strands : 0u;
+    a.words_maxw = str_pack ? strand_words_maxw(nwords) : 0;
+    a.num = a.strands ? s.n : (uint64_t) ns * s.n;
     a.steps = steps;
     a.nwords = nwords;
     a.res = s.d_res;
-    void* hdst = pin_out ? (void*) (results + 2 * s.q0) : (void*) s.h_out;
+    void* hdst = pin_out ? (void*) (results + 2 * ns * s.q0) : (void*) s.h_out;
     const bool up_ok = hipEventRecord(s.x0, s.st) == hipSuccess &&
                        (host_pack ? hipMemcpyAsync(s.dq.packed, s.h_pk, 4ull * rows * s.n, hipMemcpyHostToDevice,
                                                    s.st) == hipSuccess
                                   : hipMemcpyAsync(s.dq.ascii, hsrc, bytes, hipMemcpyHostToDevice, s.st) == hipSuccess) &&
                        hipEventRecord(s.x1, s.st) == hipSuccess &&
-                       (host_pack || a.maxw || launch_pack(&s.dq, s.st) == hipSuccess);
+                       (str_pack ? launch_strand_pack(&s.dq, s.dq.strand_words, strands, host_pack, s.st) == hipSuccess
+                                 : (host_pack || a.maxw || launch_pack(&s.dq, s.st) == hipSuccess));
     if (!up_ok || dispatch(op, K, di->nb, di->layout, a) != hipSuccess ||
-        hipMemcpyAsync(hdst, s.d_res, 8ull * s.n, hipMemcpyDeviceToHost, s.st) != hipSuccess ||
+        hipMemcpyAsync(hdst, s.d_res, 8ull * ns * s.n, hipMemcpyDeviceToHost, s.st) != hipSuccess ||
         hipEventRecord(s.done, s.st) != hipSuccess) {
       status = KFMI_E_KERNEL;
       break;
@@ -514,6 +535,19 @@ static int32_t stream_on(kfmi_dev_index* di, int member, const char* ascii, uint
 extern "C" int32_t kfmi_search_stream(void* index, const char* ascii, uint64_t num, uint32_t size,
                                       uint32_t* results, uint64_t chunk)
 {
+  return kfmi_search_stream_strands(index, ascii, num, size, results, chunk, KFMI_STRAND_FWD);
+}
+
+/* The streamed search of `strands`: FWD is kfmi_search_stream itself; REV and
+ * BOTH upload every chunk as the forward search does (ASCII or host-packed
+ * words) and write the chunk's ns * n task columns on the device, so the
+ * second strand costs no link bytes.  Results: 2 * ns u32 per read; a group
+ * member's slice of reads [a, b) is the slice results + 2 * ns * a. */
+extern "C" int32_t kfmi_search_stream_strands(void* index, const char* ascii, uint64_t num, uint32_t size,
+                                              uint32_t* results, uint64_t chunk, uint32_t strands)
+{
+  if (strands < KFMI_STRAND_FWD || strands > KFMI_STRAND_BOTH) return KFMI_E_BAD_ARGUMENT;
+  const uint32_t ns = strands == KFMI_STRAND_BOTH ? 2u : 1u;
   kfmi_fmi_t* f = (kfmi_fmi_t*) index;
   if (!f || (!ascii && num) || (!results && num)) return KFMI_E_BAD_ARGUMENT;
   DeviceGuard dg;
@@ -531,7 +565,7 @@ extern "C" int32_t kfmi_search_stream(void* index, const char* ascii, uint64_t n
   int32_t err = KFMI_SUCCESS;
   const uint32_t ftab = ftab_bases(), skip = skip_wanted();
   if (!g) {
-    err = stream_on(f->dev, 0, ascii, num, size, results, chunk, ftab, skip, ms[0], &np[0]);
+    err = stream_on(f->dev, 0, ascii, num, size, results, chunk, ftab, skip, ms[0], &np[0], strands);
   } else {
     const int n = g->n;
     uint64_t per = (num + n - 1) / n;
@@ -542,8 +576,8 @@ extern "C" int32_t kfmi_search_stream(void* index, const char* ascii, uint64_t n
     for (int i = 0; i < n; ++i) {
       const uint64_t a = per * i < num ? per * i : num, b = per * (i + 1) < num ? per * (i + 1) : num;
       th.emplace_back([&, i, a, b] {
-        errs[i] = stream_on(g->di[i], i, ascii + a * size, b - a, size, results + 2 * a, chunk, ftab, skip, ms[i],
-                              &np[i]);
+        errs[i] = stream_on(g->di[i], i, ascii + a * size, b - a, size, results + 2 * ns * a, chunk, ftab, skip,
+                            ms[i], &np[i], strands);
       });
     }
     for (auto& t : th) t.join();

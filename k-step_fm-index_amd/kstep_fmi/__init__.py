@@ -138,6 +138,11 @@ def load() -> ctypes.CDLL:
         "kfmi_locations_offsets": (vp, [vp]),
         "kfmi_locations_positions": (vp, [vp]),
         "kfmi_locations_free": (i32, [pvp]),
+        "kfmi_search_strands": (i32, [vp, vp, vp, u32]),
+        "kfmi_search_stream_strands": (i32, [vp, vp, u64, u32, vp, u64, u32]),
+        "kfmi_search_cpu_strands": (i32, [vp, vp, vp, u32, i32]),
+        "kfmi_revcomp_queries": (i32, [vp, u64, u32, vp]),
+        "kfmi_strand_words_host": (i32, [vp, u64, u32, u32, u32, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -628,16 +633,60 @@ def pack_queries_k(reads: np.ndarray, k: int) -> np.ndarray:
     return out
 
 
-def search_stream(index: Index, reads: np.ndarray, out: np.ndarray | None = None, chunk: int = 0) -> np.ndarray:
-    """Streamed search of uint8 [N, m] host reads against an index already on the
-    device (transfer_to_gpu(index, None, None)); returns uint32[2N]."""
+STRAND_FWD, STRAND_REV, STRAND_BOTH = 1, 2, 3
+
+
+def _strand_count(strands: int) -> int:
+    """Intervals per read of a strand mode (an invalid mode is left to the library's argument check)."""
+    return 2 if int(strands) == STRAND_BOTH else 1
+
+
+def revcomp(reads: np.ndarray) -> np.ndarray:
+    """Reverse strand of uint8 [N, m] reads on the host (kfmi_revcomp_queries):
+    P'[j] = "ACGT"[3 - base2index(P[m-1-j])]."""
     reads = np.ascontiguousarray(reads, dtype=np.uint8)
     n, m = reads.shape
+    out = np.empty_like(reads)
+    _check(load().kfmi_revcomp_queries(reads.ctypes.data, n, m, out.ctypes.data), "kfmi_revcomp_queries")
+    return out
+
+
+def strand_words_host(words: np.ndarray, m: int, k: int, strands: int) -> np.ndarray:
+    """kfmi_strand_words_host: the task columns of `strands` (REV / BOTH) from
+    pack_queries_k's uint32 [rows, N] forward words, by the device kernel's own
+    code run on the host; uint32 [rows, ns * N]."""
+    words = np.ascontiguousarray(words, dtype=np.uint32)
+    rows, n = words.shape
+    out = np.empty((rows, _strand_count(strands) * n), dtype=np.uint32)
+    _check(load().kfmi_strand_words_host(words.ctypes.data, n, int(m), int(k), int(strands), out.ctypes.data),
+           "kfmi_strand_words_host")
+    return out
+
+
+def search_strands(index: Index, queries: Queries, results: Results, strands: int) -> None:
+    """kfmi_search_strands: the resident search of the reads as written (STRAND_FWD),
+    of their reverse strands (STRAND_REV) or of both (STRAND_BOTH: results of
+    2 * num intervals, 2q forward, 2q + 1 reverse)."""
+    _check(load().kfmi_search_strands(index.ptr, queries.ptr, results.ptr, int(strands)), "kfmi_search_strands")
+
+
+def search_stream(index: Index, reads: np.ndarray, out: np.ndarray | None = None, chunk: int = 0,
+                  strands: int = STRAND_FWD) -> np.ndarray:
+    """Streamed search of uint8 [N, m] host reads against an index already on the
+    device (transfer_to_gpu(index, None, None)); returns uint32[2N], or
+    uint32[4N] for strands=STRAND_BOTH (interval 2q forward, 2q + 1 reverse)."""
+    reads = np.ascontiguousarray(reads, dtype=np.uint8)
+    n, m = reads.shape
+    ns = _strand_count(strands)
     if out is None:
-        out = np.empty(2 * n, dtype=np.uint32)
-    assert out.dtype == np.uint32 and out.flags.c_contiguous and out.size >= 2 * n
-    _check(load().kfmi_search_stream(index.ptr, reads.ctypes.data, n, m, out.ctypes.data, int(chunk)),
-           "kfmi_search_stream")
+        out = np.empty(2 * ns * n, dtype=np.uint32)
+    assert out.dtype == np.uint32 and out.flags.c_contiguous and out.size >= 2 * ns * n
+    if int(strands) == STRAND_FWD:
+        _check(load().kfmi_search_stream(index.ptr, reads.ctypes.data, n, m, out.ctypes.data, int(chunk)),
+               "kfmi_search_stream")
+    else:
+        _check(load().kfmi_search_stream_strands(index.ptr, reads.ctypes.data, n, m, out.ctypes.data, int(chunk),
+                                                 int(strands)), "kfmi_search_stream_strands")
     return out
 
 
@@ -646,31 +695,47 @@ def search_cpu(index: Index, queries: Queries, results: Results, nthreads: int =
     _check(load().kfmi_search_cpu(index.ptr, queries.ptr, results.ptr, int(nthreads)), "searchIndexCPU")
 
 
-def search_cpu_array(index: Index, queries: np.ndarray, nthreads: int = 0) -> np.ndarray:
-    """One-shot host search of uint8 [N, m] reads (searchIndexCPU); uint32[2N]."""
+def search_cpu_strands(index: Index, queries: Queries, results: Results, strands: int, nthreads: int = 0) -> None:
+    """kfmi_search_cpu_strands: the host search of the strands' tasks."""
+    _check(load().kfmi_search_cpu_strands(index.ptr, queries.ptr, results.ptr, int(strands), int(nthreads)),
+           "kfmi_search_cpu_strands")
+
+
+def search_cpu_array(index: Index, queries: np.ndarray, nthreads: int = 0, strands: int = STRAND_FWD) -> np.ndarray:
+    """One-shot host search of uint8 [N, m] reads (searchIndexCPU); uint32[2N]
+    (uint32[4N] for strands=STRAND_BOTH)."""
     q = Queries.from_array(queries)
-    r = Results.alloc(queries.shape[0])
+    r = Results.alloc(_strand_count(strands) * queries.shape[0])
     try:
-        search_cpu(index, q, r, nthreads)
+        if int(strands) == STRAND_FWD:
+            search_cpu(index, q, r, nthreads)
+        else:
+            search_cpu_strands(index, q, r, strands, nthreads)
         return r.array().copy()
     finally:
         q.close()
         r.close()
 
 
-def search_array(index: Index, queries: np.ndarray, backend: str | None = None) -> np.ndarray:
-    """One-shot GPU search of uint8 [N, m] reads; returns uint32[2N]."""
+def search_array(index: Index, queries: np.ndarray, backend: str | None = None,
+                 strands: int = STRAND_FWD) -> np.ndarray:
+    """One-shot GPU search of uint8 [N, m] reads; returns uint32[2N]
+    (uint32[4N] for strands=STRAND_BOTH)."""
     if backend:
         set_backend(backend)
     q = Queries.from_array(queries)
-    r = Results.alloc(queries.shape[0])
-    transfer_to_gpu(index, q, r)
-    search(index, q, r)
-    transfer_to_cpu(r)
-    out = r.array().copy()
-    q.close()
-    r.close()
-    return out
+    r = Results.alloc(_strand_count(strands) * queries.shape[0])
+    try:
+        transfer_to_gpu(index, q, r)
+        if int(strands) == STRAND_FWD:
+            search(index, q, r)
+        else:
+            search_strands(index, q, r, strands)
+        transfer_to_cpu(r)
+        return r.array().copy()
+    finally:
+        q.close()
+        r.close()
 
 
 def env_int(name: str, default: int) -> int:
