@@ -489,6 +489,15 @@ int32_t kfmi_revcomp_queries(const char *ascii, uint64_t num, uint32_t size, cha
  * kfmi_pack_queries_k of kfmi_revcomp_queries of the read. */
 int32_t kfmi_strand_words_host(const uint32_t *words, uint64_t num, uint32_t size, uint32_t k,
                                uint32_t strands, uint32_t *out);
+/* Test accessor (host only, no device): reverse_stream<maxw> of every column of
+ * `words` -- the register form of the same identity, which the kernels that
+ * pack from ASCII rows run (the fused strand kernel and the whole-row strand
+ * pack).  words and out are maxw x num, 16 bases per word, word-major; a
+ * column holds the forward code words of a read of `size` bases, zero above
+ * base size-1.  maxw must be 8 or 16 and 1 <= size <= 16 * maxw, else
+ * KFMI_E_BAD_ARGUMENT. */
+int32_t kfmi_reverse_stream_host(const uint32_t *words, uint64_t num, uint32_t size, uint32_t maxw,
+                                 uint32_t *out);
 
 /* Diagnostic (not in the reference): replays the line requests a
  * task-mid / coop-mid search of `queries` makes (MID128 layout, K = 2, d = 64,

@@ -172,6 +172,31 @@ extern "C" int32_t kfmi_strand_words_host(const uint32_t* words, uint64_t num, u
   return KFMI_SUCCESS;
 }
 
+template <int MAXW>
+static void reverse_stream_columns(const uint32_t* words, uint64_t num, uint32_t size, uint32_t* out)
+{
+  for (uint64_t c = 0; c < num; ++c) {
+    uint32_t s[MAXW], rv[MAXW];
+    for (int w = 0; w < MAXW; ++w) s[w] = words[(uint64_t) w * num + c];
+    reverse_stream<MAXW>(s, size, rv);
+    for (int w = 0; w < MAXW; ++w) out[(uint64_t) w * num + c] = rv[w];
+  }
+}
+
+/* Test accessor: reverse_stream<maxw>, the register form that both ASCII-fed
+ * device kernels (task_strands_kernel, pack_strands_rows_kernel) run, on the
+ * host: column c of `words` ([maxw][num], 16 bases per word, zero above base
+ * size-1) -> column c of `out`, same shape. */
+extern "C" int32_t kfmi_reverse_stream_host(const uint32_t* words, uint64_t num, uint32_t size, uint32_t maxw,
+                                            uint32_t* out)
+{
+  if ((maxw != 8 && maxw != 16) || size == 0 || size > 16u * maxw || ((!words || !out) && num))
+    return KFMI_E_BAD_ARGUMENT;
+  if (maxw == 8) reverse_stream_columns<8>(words, num, size, out);
+  else reverse_stream_columns<16>(words, num, size, out);
+  return KFMI_SUCCESS;
+}
+
 /* The task columns of dq's reads into `out` ((nwords + 1) x ns * num words),
  * queued on st: from the ASCII reads when the device has them, else from the
  * forward code words in dq->packed. */

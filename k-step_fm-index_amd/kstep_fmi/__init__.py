@@ -143,6 +143,7 @@ def load() -> ctypes.CDLL:
         "kfmi_search_cpu_strands": (i32, [vp, vp, vp, u32, i32]),
         "kfmi_revcomp_queries": (i32, [vp, u64, u32, vp]),
         "kfmi_strand_words_host": (i32, [vp, u64, u32, u32, u32, vp]),
+        "kfmi_reverse_stream_host": (i32, [vp, u64, u32, u32, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -660,6 +661,20 @@ def strand_words_host(words: np.ndarray, m: int, k: int, strands: int) -> np.nda
     out = np.empty((rows, _strand_count(strands) * n), dtype=np.uint32)
     _check(load().kfmi_strand_words_host(words.ctypes.data, n, int(m), int(k), int(strands), out.ctypes.data),
            "kfmi_strand_words_host")
+    return out
+
+
+def reverse_stream_host(words: np.ndarray, m: int, maxw: int) -> np.ndarray:
+    """kfmi_reverse_stream_host: reverse_stream<maxw> (the register form the
+    ASCII-fed strand kernels run) of every column of uint32 [maxw, N] forward
+    code words, 16 bases per word, zero above base m-1; uint32 [maxw, N]."""
+    words = np.ascontiguousarray(words, dtype=np.uint32)
+    rows, n = words.shape
+    if rows != int(maxw):
+        raise KfmiError(33, "kfmi_reverse_stream_host")
+    out = np.empty((rows, n), dtype=np.uint32)
+    _check(load().kfmi_reverse_stream_host(words.ctypes.data, n, int(m), int(maxw), out.ctypes.data),
+           "kfmi_reverse_stream_host")
     return out
 
 

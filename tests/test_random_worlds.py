@@ -20,11 +20,17 @@ restatement refuses a search that reads past the file), else against the
 host search and kept below the cap (tests/test_ac_drift.py).  A geometry a
 backend does not take must be refused with code 33, never answered.
 The host search (searchIndexCPU) runs in the CPU suite; the GPU
-backends in the GPU suite."""
+backends in the GPU suite.
+Strand searches (REV, BOTH) run on every fourth world, host and GPU, against
+the brute-force interval of the read's reverse complement as numpy defines it
+(tests/strand_reads.py), not as the library computes it."""
+from functools import lru_cache
+
 import numpy as np
 import pytest
 
 import util
+from strand_reads import revcomp_def
 
 PLAIN = ("task", "coop", "task-mid", "coop-mid")
 ALT = ("task-ac", "coop-ac", "task-ac-mid", "coop-ac-mid")
@@ -185,6 +191,73 @@ def test_random_world_gpu(kfmi_mod, oracle_mod, i):
     finally:
         for x in (idx,) + acs:
             x.close()
+
+
+@lru_cache(maxsize=None)
+def strand_world(i):
+    """world(i) with the brute-force intervals of the reverse strands, by the
+    numpy definition of the reverse complement (tests/strand_reads.py), and the
+    two interleaved as STRAND_BOTH returns them.  Shared by the host and the
+    GPU leg; nobody writes to the arrays."""
+    n, k, d, m, text, q, fwd = world(i)
+    bf = util.BruteForce(text.decode())
+    rev = np.array([x for r in revcomp_def(q) for x in bf.interval(r.tobytes())], dtype=np.uint32)
+    both = np.empty((2 * q.shape[0], 2), np.uint32)
+    both[0::2], both[1::2] = fwd.reshape(-1, 2), rev.reshape(-1, 2)
+    for a in (q, fwd, rev, both):
+        a.setflags(write=False)
+    return n, k, d, m, text, q, rev, both.ravel()
+
+
+STRAND_WORLDS = range(0, WORLDS, 4)
+
+
+@pytest.mark.parametrize("i", STRAND_WORLDS)
+def test_random_world_strands_host_search(kfmi_mod, i):
+    """kfmi_search_cpu_strands (REV, BOTH) on every fourth world, its index and
+    the tag-101 interleaving, against brute force on the reverse complement."""
+    K = kfmi_mod
+    n, k, d, m, text, q, rev, both = strand_world(i)
+    idx = K.Index.build(text, k=k, d=d)
+    try:
+        for tagged in (idx, idx.interleave()):
+            for strands, want in ((K.STRAND_REV, rev), (K.STRAND_BOTH, both)):
+                got = K.search_cpu_array(tagged, q, 2, strands=strands)
+                assert got.shape == want.shape
+                bad = np.flatnonzero(got != want)
+                assert bad.size == 0, dict(world=i, n=n, k=k, d=d, m=m, tag=tagged.header()["tag"], strands=strands,
+                                           first=int(bad[0]))
+    finally:
+        idx.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("i", STRAND_WORLDS)
+def test_random_world_strands_gpu(kfmi_mod, i):
+    """Strand searches (REV, BOTH) under the default settings -- the auto jump
+    start and skip table, fused packing -- on every fourth world: texts of one
+    base and up, reads longer than the text, homopolymers, any d."""
+    K = kfmi_mod
+    if K.device_count() < 1:
+        pytest.fail("no HIP device visible: GPU tests must run on the MI355X box")
+    K.set_device(0)
+    n, k, d, m, text, q, rev, both = strand_world(i)
+    idx = K.Index.build(text, k=k, d=d)
+    try:
+        for b in ("task", "task-mid", "coop-mid") if k <= 2 else GRP:
+            for strands, want in ((K.STRAND_REV, rev), (K.STRAND_BOTH, both)):
+                if not _takes(b, k, d, n):
+                    with pytest.raises(K.KfmiError) as e:
+                        K.search_array(idx, q, b, strands=strands)
+                    assert e.value.code == 33, (b, k, d)
+                    continue
+                got = K.search_array(idx, q, b, strands=strands)
+                assert got.shape == want.shape
+                bad = np.flatnonzero(got != want)
+                assert bad.size == 0, dict(world=i, backend=b, n=n, k=k, d=d, m=m, nq=q.shape[0], strands=strands,
+                                           first=int(bad[0]))
+    finally:
+        idx.close()
 
 
 @pytest.mark.gpu

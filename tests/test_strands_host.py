@@ -6,6 +6,9 @@
 * kfmi_search_cpu_strands(BOTH) returns at 2q the forward interval of read q
   and at 2q + 1 the forward interval of its reverse complement, both equal to
   the oracle; REV returns the latter alone; FWD is kfmi_search_cpu;
+* the code-word identity S' = ~pairreverse_m(S), in both forms the device
+  runs (word by word from packed words; the whole stream in 8 or 16
+  registers), gives the host packer's words of the reverse complement;
 * argument errors: strands outside 1..3 and a results handle too small."""
 import numpy as np
 import pytest
@@ -56,6 +59,40 @@ def test_code_word_identity_argument_errors(kfmi_mod):
         with pytest.raises(K.KfmiError) as e:
             K.strand_words_host(w, 100, k, strands)
         assert e.value.code == 33
+
+
+@pytest.mark.parametrize("maxw", [8, 16])
+def test_register_form_equals_the_host_packer_on_the_reverse_complement(kfmi_mod, maxw):
+    """reverse_stream<MAXW> (kfmi_strands.h), the register form that the fused
+    strand kernel and the whole-row strand pack run, here on the host: from a
+    read's forward words in MAXW registers (zero above base m-1) it gives the
+    host packer's words of revcomp(read), zero words above them -- every m the
+    form takes, 1 .. 16 * MAXW (every shift m % 16, every count of whole words
+    shifted out)."""
+    K = kfmi_mod
+    rng = np.random.default_rng(maxw)
+
+    def padded(words):
+        out = np.zeros((maxw, words.shape[1]), np.uint32)
+        out[:words.shape[0]] = words
+        return out
+
+    for m in range(1, 16 * maxw + 1):
+        q = np.frombuffer(b"ACGTNacgtnRx", np.uint8)[rng.integers(0, 12, size=(37, m))]
+        fwd, rev = padded(K.pack_queries_k(q, 1)), padded(K.pack_queries_k(K.revcomp(q), 1))
+        got = K.reverse_stream_host(fwd, m, maxw)
+        assert got.shape == rev.shape and np.array_equal(got, rev), m
+
+
+def test_register_form_argument_errors(kfmi_mod):
+    K = kfmi_mod
+    for maxw, m in ((4, 16), (12, 16), (32, 16), (8, 129), (16, 257), (8, 0)):
+        with pytest.raises(K.KfmiError) as e:
+            K.reverse_stream_host(np.zeros((maxw, 3), np.uint32), m, maxw)
+        assert e.value.code == 33, (maxw, m)
+    with pytest.raises(K.KfmiError) as e:                    # fewer rows than registers
+        K.reverse_stream_host(np.zeros((8, 3), np.uint32), 100, 16)
+    assert e.value.code == 33
 
 
 @pytest.fixture(scope="module")
