@@ -499,6 +499,64 @@ int32_t kfmi_strand_words_host(const uint32_t *words, uint64_t num, uint32_t siz
 int32_t kfmi_reverse_stream_host(const uint32_t *words, uint64_t num, uint32_t size, uint32_t maxw,
                                  uint32_t *out);
 
+/* ---- seed search (not in the reference, which answers for the whole read) ----
+ * Every other search returns one interval per task, the whole read's, so a
+ * read with one sequencing error gets an empty interval and nothing else.  A
+ * seed search returns the greedy right-to-left factorisation of each task
+ * into maximal exact segments (the adaptive-region seeding of GEM-style
+ * mappers): a read that yields f segments cannot align with fewer than f - 1
+ * differences, and each segment's interval is a seed for kfmi_locate.
+ *   A task is a read P of m bases on one strand (KFMI_STRAND_REV tasks are the
+ * read P' above and their coordinates are those of P').  With K the index's
+ * step count (1 or 2) and rem = m % K, the units of a task are, from the right,
+ * its last rem bases (if rem > 0) and then consecutive groups of K bases down
+ * to base 0.  With e = m and S = max_seeds, while e > 0 and fewer than S
+ * records exist:
+ *   1. take the unit ending at e; if that unit alone does not occur in the
+ *      text (tiny or low-complexity texts only), set e to its start, emit
+ *      nothing and go on;
+ *   2. else extend leftwards unit by unit while the substring still occurs,
+ *      b the start of the longest such substring P[b .. e);
+ *   3. emit the record {L, R, start = b, len = e - b}, [L, R) the suffix-array
+ *      interval of P[b .. e) -- the integers the forward search of that
+ *      substring returns on this backend -- and set e = b.
+ * "Occurs" is R > L.  The granularity is the index's K: at K = 2 a segment ends
+ * on a 2-base boundary counted from the right end (after the rem bases), so it
+ * can stop one base short of the longest match; that is what the K-step walk
+ * decides without a second index.  A task whose whole-read interval is not
+ * empty yields exactly the one record {that interval, 0, m}; max_seeds = 1 asks
+ * how deep a read matches from its right end and where that suffix occurs.
+ *   `intervals` and `spans` are two ordinary results handles of S * ns * num
+ * entries each (kfmi_results_alloc, transferred as usual; ns = 1 for FWD and
+ * REV, 2 for BOTH) and must be exactly that large.  Slot t * S + s holds
+ * record s of task t -- in BOTH t = 2q + strand, as for kfmi_search_strands --
+ * as (L, R) in `intervals` and (start, len) in `spans`; the slots a task does
+ * not use are written as zeros in both by the search itself, whatever they held.
+ * Task-major, so a slice of reads is a contiguous slice of results.  Two
+ * handles, so kfmi_locate(index, intervals, max_occ, ..) works unchanged: it
+ * sees S * ns * num intervals, the empty ones without positions;
+ * transferGPUtoCPU moves each handle.
+ *   kfmi_search_seeds: the plain-counter task backends ("task", "task-mid") at
+ * K = 1, 2, reads of 1 .. 256 bases with any m % K, every strand mode, fused
+ * packing on or off, ASCII and KFMI_UPLOAD=packed uploads, one device.  The
+ * jump-start and skip tables are used where the settings put them in effect
+ * (each new segment may take them again) and never change a result.  Returns
+ * KFMI_E_BAD_ARGUMENT for max_seeds outside 1 .. 8, an unknown `strands`,
+ * handles of another size and reads over 256 bases; KFMI_E_NOT_IMPLEMENTED for
+ * the coop and AltCounters backends, K = 3 / 4 and device-group handles.  A
+ * refused call writes nothing.  kfmi_last_timing as for kfmi_search.  REV and
+ * BOTH searches that take the pack launch (fused packing off, m % K != 0,
+ * host-packed uploads) use the queries handle's strand words, so the rule of
+ * kfmi_search_strands holds: not two of them on ONE queries handle at a time.
+ *   kfmi_search_seeds_cpu: the same tasks on the host (searchIndexCPU's LF step
+ * and remainder table; a temporary holds the reverse complements), index tags
+ * 100 / 101; AltCounters images return KFMI_E_BAD_ARGUMENT.  nthreads as for
+ * kfmi_search_cpu. */
+int32_t kfmi_search_seeds(void *index, void *queries, void *intervals, void *spans,
+                          uint32_t max_seeds, uint32_t strands);
+int32_t kfmi_search_seeds_cpu(void *index, void *queries, void *intervals, void *spans,
+                              uint32_t max_seeds, uint32_t strands, int32_t nthreads);
+
 /* Diagnostic (not in the reference): replays the line requests a
  * task-mid / coop-mid search of `queries` makes (MID128 layout, K = 2, d = 64,
  * m % K == 0, both uploaded) without the LF chain's dependence: a trace launch

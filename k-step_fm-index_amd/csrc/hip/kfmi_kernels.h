@@ -273,6 +273,128 @@ __device__ __forceinline__ void skip_walk(const IdxArgs& ix, const uint32_t (&cw
   Rq = R[0];
 }
 
+/* The walk of a seed search (kfmi_seeds.hip, kstep_fmi.h section 2, DESIGN.md
+ * 5g): the greedy right-to-left factorisation of one task into maximal exact
+ * segments, on skip_walk's frame -- the same code words in LDS, the same
+ * per-lane `pos`, one line per lane and round.  A task of m bases has the
+ * units, from the right, of its last rem = m % K bases and then of K bases
+ * each; `mk` = m - rem, and after `pos` K-steps the walk stands at base
+ * b = mk - K * pos.  Beside [L, R) a lane keeps the end `e` of its segment
+ * (e == b: nothing matched yet, [L, R) is the full interval), the interval it
+ * had before the round's step, and its record count.
+ *   When a step leaves R <= L the segment P[b .. e) is maximal: the lane stores
+ * {previous L, R} into iv[cnt] and {b, e - b} into sp[cnt] -- as the record
+ * completes, at a runtime address, so no register array is indexed by cnt --
+ * and starts again from [0, bwtsize) at the same pos.  When the step started
+ * from the full interval the unit alone does not occur: nothing is stored and
+ * the lane moves on by one unit.  A new segment may take the tables again: a
+ * lane on the full interval looks up the jump-start table with the window
+ * `code` (its low 2K * ftab_steps bits are the table's index), a lane on one
+ * row the skip table; both tables are uint2, so a round's lookup is one load
+ * either way.  An empty jump-start entry only says that the segment ends
+ * within those steps, not where, and a differing skip entry the same: the lane
+ * takes the ordinary steps until its segment ends (`dead`).
+ *   The loop ends when no lane has steps or free slots left; the segment that
+ * reaches base 0 is stored then, and the slots a task did not use are zeroed.
+ * Start: pos = 0 and [L, R), e from the caller -- the remainder-table entry
+ * with e = m where it is not empty, else the full interval with e = mk. */
+template <class G, int MAXW, int SPLIT>
+__device__ __forceinline__ void seed_walk(const IdxArgs& ix, const uint32_t (&cw)[MAXW], uint32_t steps, uint32_t mk,
+                                          uint32_t Lq, uint32_t Rq, uint32_t e, uint32_t S, uint2* __restrict__ iv,
+                                          uint2* __restrict__ sp)
+{
+  static_assert(G::K <= 2 && MAXW > 0, "seed search: task kernels at K <= 2");
+  extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  uint32_t* cl = reinterpret_cast<uint32_t*>(stage) + wv * (64u * MAXW) + lane;
+#pragma unroll
+  for (int k = 0; k < MAXW; ++k) cl[64 * k] = cw[k];
+  const uint32_t J = ix.skip_steps, F = ix.ftab ? ix.ftab_steps : 0u;
+  const int grp = (int) lane / 16;
+  uint32_t L[1] = {Lq}, R[1] = {Rq};
+  uint32_t pos = 0, cnt = 0;
+  bool dead = false;   /* a lookup failed: the ordinary steps until this segment ends */
+  while (__ballot(pos < steps && cnt < S)) {
+    const bool act = pos < steps && cnt < S;
+    const uint32_t bit = pos * (2u * G::K), k = bit >> 5;
+    const uint32_t lo = k < (uint32_t) MAXW ? cl[64u * k] : 0u;
+    const uint32_t hi = k + 1u < (uint32_t) MAXW ? cl[64u * (k + 1u)] : 0u;
+    const uint32_t code = __builtin_amdgcn_alignbit(hi, lo, bit & 31u);   /* the stream from step `pos` on */
+    const uint32_t b = mk - (uint32_t) G::K * pos;
+    const bool fresh = e == b;
+    const bool jump = act && !dead && fresh && F != 0u && pos + F <= steps;
+    const bool one = act && !dead && !fresh && R[0] == L[0] + 1u && L[0] < ix.skip_rows && pos + J <= steps;
+    const bool look = one || jump;
+    const uint2* tp = one ? ix.skip + L[0] : ix.ftab + (jump ? code & ix.ftab_mask : 0u);
+    uint2 te = make_uint2(SKIP_NONE, 0u);
+    if (ix.skip_split == 4u) {   /* wave-uniform: at most 16 pages per gather instruction */
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+        if (look && grp == g) te = *tp;
+    } else if (look) {
+      te = *tp;
+    }
+    if (act && !look) {
+      const uint32_t pL = L[0], pR = R[0];
+      uint32_t c[1] = {code & (uint32_t) (G::NC - 1)};
+      uint32_t sx[2 * G::K];
+      plane_xor<G::K>(c[0], sx);
+      if constexpr (G::SMALL) {
+        Blk<G> kl[1], kr[1];
+        fetch_ends_split<G, 1, SPLIT>(ix, L, R, c, kl, kr);
+        L[0] = lf_from_block<G>(ix, kl[0], L[0], c[0], sx);
+        R[0] = lf_from_block<G>(ix, kr[0], R[0], c[0], sx);
+      } else {
+        L[0] = lf_stream<G>(ix, L[0], c[0], sx);
+        R[0] = lf_stream<G>(ix, R[0], c[0], sx);
+      }
+      if (R[0] <= L[0]) {   /* the segment ends at b */
+        if (fresh) {        /* this unit alone does not occur: past it, no record */
+          ++pos;
+          e = b - (uint32_t) G::K;
+        } else {
+          iv[cnt] = make_uint2(pL, pR);
+          sp[cnt] = make_uint2(b, e - b);
+          ++cnt;
+          e = b;
+        }
+        L[0] = 0u;
+        R[0] = ix.bwtsize;
+        dead = false;
+      } else {
+        ++pos;
+      }
+    }
+    if (one) {
+      if (te.x != SKIP_NONE && te.y == code) {
+        L[0] = te.x;
+        R[0] = te.x + 1u;
+        pos += J;
+      } else {
+        dead = true;
+      }
+    } else if (jump) {
+      if (te.y > te.x) {
+        L[0] = te.x;
+        R[0] = te.y;
+        pos += F;
+      } else {
+        dead = true;
+      }
+    }
+  }
+  const uint32_t b = mk - (uint32_t) G::K * pos;   /* 0 unless the slots ran out */
+  if (cnt < S && e != b) {
+    iv[cnt] = make_uint2(L[0], R[0]);
+    sp[cnt] = make_uint2(b, e - b);
+    ++cnt;
+  }
+  for (; cnt < S; ++cnt) {
+    iv[cnt] = make_uint2(0u, 0u);
+    sp[cnt] = make_uint2(0u, 0u);
+  }
+}
+
 /* SKIP (last template value, fused K <= 2 only): the walk with the skip table,
  * launched when ix.skip is set; without it the kernel is the plain walk. */
 template <class G, int QPT, int MAXW, int SPLIT = 1, bool SKIP = false>
@@ -479,6 +601,77 @@ __global__ __launch_bounds__(256) void task_strands_kernel(IdxArgs ix, const uin
   }
   skip_walk<G, MAXW, SPLIT>(ix, cw, steps, skip, L, R);
   *reinterpret_cast<uint2*>(res + 2 * t) = make_uint2(L, R);
+}
+
+/* Seed search (kfmi_seeds.hip): task t's start state and its
+ * walk.  The last rem bases are one unit: a remainder-table entry that is not
+ * empty starts the first segment at base m, an empty one means that unit does
+ * not occur and the walk starts past it.  The jump start is seed_walk's own
+ * first round.  Slot t * S + s of either array is record s of task t. */
+template <class G, int MAXW, int SPLIT>
+__device__ __forceinline__ void seed_task(const IdxArgs& ix, const uint32_t (&cw)[MAXW], uint32_t rc, uint32_t m,
+                                          uint32_t steps, uint64_t t, uint32_t S, uint32_t* __restrict__ res,
+                                          uint32_t* __restrict__ spans)
+{
+  const uint32_t mk = m - ix.rem;
+  uint32_t L = 0, R = ix.bwtsize, e = mk;
+  if (ix.rem) {   /* wave-uniform */
+    const uint2 lr = ix.rtab[rc];
+    if (lr.y > lr.x) {
+      L = lr.x;
+      R = lr.y;
+      e = m;
+    }
+  }
+  seed_walk<G, MAXW, SPLIT>(ix, cw, steps, mk, L, R, e, S, reinterpret_cast<uint2*>(res) + t * S,
+                            reinterpret_cast<uint2*>(spans) + t * S);
+}
+
+/* The three seed kernels: an existing staging each, then seed_task.  They are
+ * launched with or without a skip table.
+ * Forward reads, fused packing: task_kernel's staging (m <= 16 * MAXW, any rem). */
+template <class G, int MAXW, int SPLIT>
+__global__ __launch_bounds__(256) void seed_kernel(IdxArgs ix, const uint8_t* __restrict__ ascii, uint32_t m,
+                                                   uint64_t num, uint32_t steps, uint32_t S,
+                                                   uint32_t* __restrict__ res, uint32_t* __restrict__ spans)
+{
+  extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
+  uint32_t cw[MAXW];
+  uint32_t rc = 0;
+  stage_query_codes<MAXW>(ascii, num, m, stage, cw, ix.rem, rc);   /* whole block, before any exit */
+  const uint64_t t = (uint64_t) blockIdx.x * 256 + threadIdx.x;
+  if (t >= num) return;
+  seed_task<G, MAXW, SPLIT>(ix, cw, rc, m, steps, t, S, res, spans);
+}
+
+/* Either strand or both, fused packing: task_strands_kernel's staging (m % K == 0). */
+template <class G, int MAXW, int SPLIT>
+__global__ __launch_bounds__(256) void seed_strands_kernel(IdxArgs ix, const uint8_t* __restrict__ ascii, uint32_t m,
+                                                           uint64_t num, uint32_t steps, uint32_t strands, uint32_t S,
+                                                           uint32_t* __restrict__ res, uint32_t* __restrict__ spans)
+{
+  extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
+  uint32_t cw[MAXW];
+  stage_strand_codes<MAXW>(ascii, num, m, stage, cw, strands);   /* whole block, before any exit */
+  const uint64_t t = (uint64_t) blockIdx.x * 256 + threadIdx.x;
+  if (t >= (strands == 3u ? 2u : 1u) * num) return;
+  seed_task<G, MAXW, SPLIT>(ix, cw, 0u, m, steps, t, S, res, spans);
+}
+
+/* Code words a pack launch or the host wrote (num task columns of qp, row
+ * nwords the remainder codes): task_words_skip_kernel's loads. */
+template <class G, int MAXW, int SPLIT>
+__global__ __launch_bounds__(256) void seed_words_kernel(IdxArgs ix, const uint32_t* __restrict__ qp, uint32_t m,
+                                                         uint64_t num, uint32_t steps, uint32_t nwords, uint32_t S,
+                                                         uint32_t* __restrict__ res, uint32_t* __restrict__ spans)
+{
+  const uint64_t t = (uint64_t) blockIdx.x * 256 + threadIdx.x;
+  if (t >= num) return;
+  uint32_t cw[MAXW];
+#pragma unroll
+  for (int k = 0; k < MAXW; ++k) cw[k] = (uint32_t) k < nwords ? qp[(uint64_t) k * num + t] : 0u;
+  const uint32_t rc = ix.rem ? qp[(uint64_t) nwords * num + t] & ((1u << (2u * ix.rem)) - 1u) : 0u;
+  seed_task<G, MAXW, SPLIT>(ix, cw, rc, m, steps, t, S, res, spans);
 }
 
 /* ftab construction: [L, R) of every code stream v of ftab_steps K-steps
@@ -777,6 +970,10 @@ struct SearchLaunch {
   uint64_t num;
   uint32_t steps, nwords;
   uint32_t* res;
+  /* seed searches (launch_seeds): res holds the intervals and spans the {start, len} pairs, max_seeds slots
+     per task in each; maxw / words_maxw / strands as for a strand search, strands 0 = forward */
+  uint32_t* spans;
+  uint32_t max_seeds;
   /* locate */
   const uint32_t* sa;
   uint32_t sa_log2;
@@ -881,6 +1078,60 @@ static hipError_t launch_task(const SearchLaunch& a)
   }
   launch_task_split<G, 1>(a);
   return hipGetLastError();
+}
+
+/* Seed searches: the kernel by where the code words come from -- fused packing
+ * (a.maxw; a.strands 2 / 3 the strand staging on a.num reads), else the
+ * a.num task columns in a.qp (a.words_maxw registers). */
+template <class G, int SPLIT>
+static void launch_seeds_split(const SearchLaunch& a)
+{
+#define KFMI_SEED_MAXW(MW, KERNEL, GRID, LDS, ...)                                                           \
+  do {                                                                                                       \
+    if ((MW) == 8)                                                                                           \
+      hipLaunchKernelGGL((KERNEL<G, 8, SPLIT>), dim3((uint32_t) (GRID)), dim3(256), LDS, a.st, __VA_ARGS__); \
+    else                                                                                                     \
+      hipLaunchKernelGGL((KERNEL<G, 16, SPLIT>), dim3((uint32_t) (GRID)), dim3(256), LDS, a.st, __VA_ARGS__); \
+  } while (0)
+  if (a.maxw) {   /* LDS: the staging, then 64 x maxw code words per wave */
+    const size_t lds = std::max((size_t) 4 * stage_slot_bytes(a.m), (size_t) 4 * 64 * 4 * (size_t) a.maxw);
+    if (a.strands) {
+      const uint64_t tblocks = ((a.strands == 3u ? 2u : 1u) * a.num + 255) / 256;
+      KFMI_SEED_MAXW(a.maxw, seed_strands_kernel, tblocks, lds, a.ix, a.ascii, a.m, a.num, a.steps, a.strands,
+                     a.max_seeds, a.res, a.spans);
+    } else {
+      KFMI_SEED_MAXW(a.maxw, seed_kernel, (a.num + 255) / 256, lds, a.ix, a.ascii, a.m, a.num, a.steps, a.max_seeds,
+                     a.res, a.spans);
+    }
+  } else {
+    const size_t lds = (size_t) 4 * 64 * 4 * (size_t) a.words_maxw;
+    KFMI_SEED_MAXW(a.words_maxw, seed_words_kernel, (a.num + 255) / 256, lds, a.ix, a.qp, a.m, a.num, a.steps,
+                   a.nwords, a.max_seeds, a.res, a.spans);
+  }
+#undef KFMI_SEED_MAXW
+}
+
+/* The fetch form is launch_task's for the same geometry and table size class. */
+template <class G>
+static hipError_t launch_seeds(const SearchLaunch& a)
+{
+  if constexpr (G::K <= 2 && (G::LAY == LAY_INTER || G::LAY == LAY_MID)) {
+    const int mw = a.maxw ? a.maxw : a.words_maxw;
+    if (mw != 8 && mw != 16) return hipErrorInvalidValue;
+    const uint32_t want = a.ix.split;
+    if constexpr (G::SMALL && X4<G>::OK) {   /* each geometry gets only the forms it can be launched with */
+      if (want == 1) launch_seeds_split<G, 8>(a);
+      else launch_seeds_split<G, 7>(a);
+    } else if constexpr (G::SMALL) {
+      if (want == 4 || (want == 2 && mw == 8)) launch_seeds_split<G, 4>(a);
+      else launch_seeds_split<G, 1>(a);
+    } else {
+      launch_seeds_split<G, 1>(a);
+    }
+    return hipGetLastError();
+  } else {
+    return hipErrorInvalidValue;
+  }
 }
 
 template <class G>
@@ -1021,6 +1272,18 @@ hipError_t dispatch_one(Op op, const SearchLaunch& a, unsigned long long* d_tota
   template hipError_t dispatch_one<KK, NBV, LAYV>(Op, const SearchLaunch&, unsigned long long*);
 #define KFMI_EXTERN(KK, NBV, LAYV) \
   extern template hipError_t dispatch_one<KK, NBV, LAYV>(Op, const SearchLaunch&, unsigned long long*);
+
+/* The seed kernels' launch, apart from dispatch_one so that the units above
+ * stay as they are: instantiated per (K, NB, LAY) in kfmi_inst_seeds_*.hip for
+ * K <= 2 on the task and task-mid layouts, called from kfmi_seeds.hip. */
+template <int K, int NB, int LAY>
+hipError_t seeds_one(const SearchLaunch& a)
+{
+  return launch_seeds<Geo<K, NB, LAY>>(a);
+}
+
+#define KFMI_SEEDS_INSTANTIATE(KK, NBV, LAYV) template hipError_t seeds_one<KK, NBV, LAYV>(const SearchLaunch&);
+#define KFMI_SEEDS_EXTERN(KK, NBV, LAYV) extern template hipError_t seeds_one<KK, NBV, LAYV>(const SearchLaunch&);
 
 }  // namespace kfmi
 

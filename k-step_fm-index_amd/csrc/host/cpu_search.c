@@ -356,6 +356,102 @@ void searchIndexCPU(void *index, void *queries, void *resIntervals)
   cs_search_team((kfmi_fmi_t *) index, (kfmi_qrys_t *) queries, (kfmi_res_t *) resIntervals);
 }
 
+/* Seed search on the host (kstep_fmi.h section 2): one task's
+ * greedy right-to-left factorisation into maximal exact segments, with this
+ * file's LF step and remainder table.  The units are the last m % K bases and
+ * then K bases each; b is the base the walk stands at, e the end of the
+ * current segment (e == b: nothing matched yet).  iv / sp: the task's S slots. */
+static void cs_seed_task(const cs_idx_t *ix, const uint8_t *p, uint32_t m, const uint32_t *rtab, uint32_t S,
+                         uint32_t *iv, uint32_t *sp)
+{
+  const uint32_t K = ix->K, rem = m % K;
+  uint32_t L = 0, R = ix->bwtsize, b = m - rem, e = b, cnt = 0;
+  if (rem) {   /* an empty entry: the unit does not occur, the walk starts past it */
+    const uint32_t x = cs_kmer(p, (int64_t) m - 1, rem);
+    if (rtab[2 * x + 1] > rtab[2 * x]) {
+      L = rtab[2 * x];
+      R = rtab[2 * x + 1];
+      e = m;
+    }
+  }
+  while (b > 0 && cnt < S) {
+    const uint32_t c = cs_kmer(p, (int64_t) b - 1, K);
+    const uint32_t nL = cs_lf(ix, K, ix->NB, ix->inter, 0, L, c), nR = cs_lf(ix, K, ix->NB, ix->inter, 0, R, c);
+    if (nR > nL) {
+      L = nL;
+      R = nR;
+      b -= K;
+      continue;
+    }
+    if (e == b) {   /* this unit alone does not occur */
+      b -= K;
+      e = b;
+    } else {        /* P[b .. e) is maximal */
+      iv[2 * cnt] = L;
+      iv[2 * cnt + 1] = R;
+      sp[2 * cnt] = b;
+      sp[2 * cnt + 1] = e - b;
+      ++cnt;
+      e = b;
+    }
+    L = 0;
+    R = ix->bwtsize;
+  }
+  if (cnt < S && e != b) {   /* the segment that reached base 0 */
+    iv[2 * cnt] = L;
+    iv[2 * cnt + 1] = R;
+    sp[2 * cnt] = b;
+    sp[2 * cnt + 1] = e - b;
+    ++cnt;
+  }
+  for (; cnt < S; ++cnt) iv[2 * cnt] = iv[2 * cnt + 1] = sp[2 * cnt] = sp[2 * cnt + 1] = 0;
+}
+
+int32_t kfmi_search_seeds_cpu(void *index, void *queries, void *intervals, void *spans, uint32_t max_seeds,
+                              uint32_t strands, int32_t nthreads)
+{
+  kfmi_fmi_t *f = (kfmi_fmi_t *) index;
+  const kfmi_qrys_t *q = (const kfmi_qrys_t *) queries;
+  kfmi_res_t *ri = (kfmi_res_t *) intervals, *rs = (kfmi_res_t *) spans;
+  const int nt = nthreads > 0 ? nthreads : (getenv("OMP_NUM_THREADS") ? omp_get_max_threads() : kfmi_process_cpus());
+  const uint32_t S = max_seeds;
+  cs_idx_t ix;
+  uint32_t rtab[2 * 64], ns;
+  char *rev = NULL;
+  int64_t ntasks, t;
+  int32_t err;
+  if (S < 1 || S > 8 || strands < KFMI_STRAND_FWD || strands > KFMI_STRAND_BOTH) return KFMI_E_BAD_ARGUMENT;
+  if (!f || !q || !ri || !rs || ri == rs || q->size == 0 || q->size > 256) return KFMI_E_BAD_ARGUMENT;
+  ns = strands == KFMI_STRAND_BOTH ? 2u : 1u;
+  if (ri->num != (uint64_t) S * ns * q->num || rs->num != ri->num) return KFMI_E_BAD_ARGUMENT;
+  if (q->num && (!q->h_queries || !ri->h_results || !rs->h_results)) return KFMI_E_BAD_ARGUMENT;
+  if (f->tag != KFMI_INDEX_VER_BASELINE && f->tag != KFMI_INDEX_VER_INTERLEAVE) return KFMI_E_BAD_ARGUMENT;
+  err = kfmi_host_entries(f);
+  if (!err) err = cs_setup(f, q, ri, &ix);
+  if (err) return err;
+  if (q->size % ix.K) cs_rem_table(&ix, q->size % ix.K, rtab);
+  if (strands != KFMI_STRAND_FWD && q->num) {   /* the host search is not the hot path: P' written out */
+    rev = (char *) kfmi_big_alloc(q->num * (uint64_t) q->size + 1);
+    if (!rev) return KFMI_E_ALLOCATING_MFASTA;
+    err = kfmi_revcomp_queries(q->h_queries, q->num, q->size, rev);
+    if (err) {
+      kfmi_big_free(rev);
+      return err;
+    }
+  }
+  ntasks = (int64_t) (ns * q->num);
+#pragma omp parallel for schedule(static) num_threads(nt)
+  for (t = 0; t < ntasks; ++t) {
+    const uint64_t r = ns == 2u ? (uint64_t) t >> 1 : (uint64_t) t;
+    const int back = strands == KFMI_STRAND_REV || (ns == 2u && (t & 1));
+    const uint8_t *p = (const uint8_t *) (back ? rev : q->h_queries) + r * q->size;
+    cs_seed_task(&ix, p, q->size, rtab, S, ri->h_results + 2 * (uint64_t) t * S, rs->h_results + 2 * (uint64_t) t * S);
+  }
+  kfmi_big_free(rev);
+  ri->origin = rs->origin = KFMI_RES_FROM_CPU;
+  return KFMI_SUCCESS;
+}
+
 int32_t kfmi_search_cpu(void *index, void *queries, void *results, int32_t nthreads)
 {
   int32_t err = KFMI_SUCCESS;

@@ -144,6 +144,8 @@ def load() -> ctypes.CDLL:
         "kfmi_revcomp_queries": (i32, [vp, u64, u32, vp]),
         "kfmi_strand_words_host": (i32, [vp, u64, u32, u32, u32, vp]),
         "kfmi_reverse_stream_host": (i32, [vp, u64, u32, u32, vp]),
+        "kfmi_search_seeds": (i32, [vp, vp, vp, vp, u32, u32]),
+        "kfmi_search_seeds_cpu": (i32, [vp, vp, vp, vp, u32, u32, i32]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -751,6 +753,50 @@ def search_array(index: Index, queries: np.ndarray, backend: str | None = None,
     finally:
         q.close()
         r.close()
+
+
+def search_seeds(index: Index, queries: Queries, intervals: Results, spans: Results, max_seeds: int,
+                 strands: int = STRAND_FWD) -> None:
+    """kfmi_search_seeds: every task's greedy right-to-left maximal exact
+    segments, max_seeds slots per task: slot t * max_seeds + s of `intervals`
+    holds (L, R) of record s of task t, of `spans` its (start, len); both handles
+    have max_seeds * ns * num entries and are on the device."""
+    _check(load().kfmi_search_seeds(index.ptr, queries.ptr, intervals.ptr, spans.ptr, int(max_seeds), int(strands)),
+           "kfmi_search_seeds")
+
+
+def search_seeds_cpu(index: Index, queries: Queries, intervals: Results, spans: Results, max_seeds: int,
+                     strands: int = STRAND_FWD, nthreads: int = 0) -> None:
+    """kfmi_search_seeds_cpu: the same tasks and slots on the host."""
+    _check(load().kfmi_search_seeds_cpu(index.ptr, queries.ptr, intervals.ptr, spans.ptr, int(max_seeds),
+                                        int(strands), int(nthreads)), "kfmi_search_seeds_cpu")
+
+
+def search_seeds_array(index: Index, reads: np.ndarray, backend: str | None = None, max_seeds: int = 4,
+                       strands: int = STRAND_FWD, cpu: bool = False):
+    """One-shot seed search of uint8 [N, m] reads on the GPU (cpu=True: on the
+    host); returns (intervals, spans), both uint32 [ns * N, max_seeds, 2]."""
+    if backend and not cpu:
+        set_backend(backend)
+    n, s = reads.shape[0], int(max_seeds)
+    slots = max(s, 0) * _strand_count(strands) * n
+    q = Queries.from_array(reads)
+    iv, sp = Results.alloc(slots), Results.alloc(slots)
+    try:
+        if cpu:
+            search_seeds_cpu(index, q, iv, sp, s, strands)
+        else:
+            transfer_to_gpu(index, q, iv)
+            transfer_to_gpu(index, None, sp)
+            search_seeds(index, q, iv, sp, s, strands)
+            transfer_to_cpu(iv)
+            transfer_to_cpu(sp)
+        shape = (_strand_count(strands) * n, s, 2)
+        return iv.array().copy().reshape(shape), sp.array().copy().reshape(shape)
+    finally:
+        q.close()
+        iv.close()
+        sp.close()
 
 
 def env_int(name: str, default: int) -> int:
