@@ -103,7 +103,14 @@ int32_t transferGPUtoCPU(void *results);
 /* The reads go up as ASCII (the reference's form); KFMI_UPLOAD=packed (K in
  * {1, 2, 4}) packs them to 2-bit code words on the host during the upload
  * instead -- a quarter of the PCIe bytes, a win where the host workers
- * out-pack the link; same results. */
+ * out-pack the link; same results.
+ *   An index that is on the device for another backend or device is replaced:
+ * the new copy is laid out beside the old one, which stays searchable should
+ * the upload fail -- except for lack of device memory (a K = 4 layout is 96 GB,
+ * and other handles' tables share the card).  Then the old copy is freed and
+ * the upload runs once more, so a re-layout needs room for one copy, not two;
+ * when that fails as well the call returns KFMI_E_DEVICE_ALLOC and the handle
+ * has no device copy (kfmi_device_index_bytes 0) until a later call uploads it. */
 int32_t transferCPUtoGPU(void *index, void *queries, void *results);
 /* How transferCPUtoGPU left the reads: 0 not on a device, 1 ASCII, 2 code
  * words packed by the host (a device group: its first member's slice). */
@@ -251,6 +258,63 @@ uint64_t    kfmi_device_skip_bytes(void *index);
  * each: u32 row, u32 code; row 0xFFFFFFFF = no skip from this row); entries
  * must be its row count n + 1; *steps (may be null) = J. */
 int32_t     kfmi_device_skip_table(void *index, void *out, uint64_t entries, uint32_t *steps);
+/* Text jump (not in the reference): once a search interval is the single row
+ * [i, i+1), the rest of the walk is no search any more.  One text position
+ * p = SA[i] carries the matched suffix; with t K-steps left the walk ends on
+ * [ISA[p - tK], ISA[p - tK] + 1) when p >= tK and the tK text bases before p
+ * are the read's remaining bases, and on an empty interval otherwise.  That is
+ * three lookups whatever t is -- SA[i], the packed text window, ISA[p - tK] --
+ * in two dependent round trips, where the skip table takes one per 16 bases.
+ * A lane jumps when its interval is one row and at least kfmi_set_jump_min
+ * bases remain (default 8, DESIGN.md 5a''); a lane whose compare fails goes on through the
+ * skip lookups and K-steps from the state it had, so results stay bit for bit
+ * what the walk gives, the particular empty interval included.  Such a read
+ * (one with a mismatch) pays two wasted lookups.
+ *   The tables -- the full suffix array, its inverse (4 B x rows each) and the
+ * text at 2 bits per base, 24.75 GB at 3 Gbase -- are built on the device from
+ * the uploaded index alone, with 8 B x rows more while they are built, and
+ * kept only when the build's own check finds them exact (every LF walk ends at
+ * a '$' row and rows and positions pair up one to one); a 'ref'-mode index
+ * that is no permutation gets none, which is no error.
+ *   Used by the forward per-lane search kernels with in-kernel packing (reads
+ * of up to 256 bases) on the plain layouts (task, task-mid) at K = 1, 2; the
+ * AltCounters and coop backends, K = 3 / 4, strand and seed searches, locate
+ * and the statistics calls ignore it.
+ *   kfmi_set_jump (per calling thread) / KFMI_JUMP (read once; 0, 1 or "auto"):
+ * 0 = off; KFMI_JUMP_AUTO (the default) = in effect exactly when the skip
+ * setting is auto and in effect, so kfmi_set_ftab(0), KFMI_SKIP=0 and an
+ * explicit ftab count keep naming the walks they named; the tables are then
+ * built inside transferCPUtoGPU after the auto skip table (on every member of
+ * a device group) when kfmi_jump_auto() allows it, and a failed allocation
+ * leaves them out, never an error; 1 = on whatever the other settings: built
+ * at the first search, KFMI_E_DEVICE_ALLOC when they do not fit.  Freed with
+ * the jump-start tables.  Default footprint of an uploaded 3 Gbase index with
+ * every auto table: about 86 GB (3 index + 34 ftab + 24 skip + 24.75). */
+#define KFMI_JUMP_AUTO 0xFFFFFFFFu
+#define KFMI_JUMP_MIN_DEFAULT 8u
+int32_t     kfmi_set_jump(uint32_t mode);
+/* The calling thread's setting resolved against its skip setting: 0 = off,
+ * 1 = on (explicit), 2 = auto and in effect. */
+uint32_t    kfmi_jump_in_effect(void);
+/* Fewest remaining bases a lane jumps with (process-wide, >= 1; a search reads
+ * it when it is queued), and its current value. */
+int32_t     kfmi_set_jump_min(uint32_t bases);
+uint32_t    kfmi_jump_min(void);
+/* The auto rule (pure host arithmetic): 1 when K is 1 or 2, 2 <= rows < 2^32
+ * and the build's peak, 16 * rows + 4 * ((rows - 1) / 16 + 2) bytes, is within
+ * budget_bytes (a quarter of the free device memory, or kfmi_set_ftab_budget's
+ * bytes); else 0. */
+uint32_t    kfmi_jump_auto(uint64_t rows, uint32_t K, uint64_t budget_bytes);
+/* Bytes of the text jump's tables the handle's device copies hold (all members
+ * of a device group): 8 * rows + 4 * ((rows - 1) / 16 + 2) per copy. */
+uint64_t    kfmi_device_jump_bytes(void *index);
+/* Test accessor: the tables of the single-device copy (member 0), or of member
+ * `member` of a device group, copied to sa[rows], isa[rows] (rows = n + 1;
+ * sa 0xFFFFFFFF = a row without a suffix) and text[words], words =
+ * n / 16 + 2: base n - 1 - g of the text at bits 2g of the word stream, zeros
+ * past the text.  KFMI_E_NOT_ON_DEVICE without tables. */
+int32_t     kfmi_device_jump_tables(void *index, uint32_t member, uint32_t *sa, uint32_t *isa, uint64_t rows,
+                                    uint32_t *text, uint64_t words);
 /* Test knobs of the search path (not in the reference), process-wide; their
  * environment variables are read once, at the first search, and these setters
  * switch them afterwards.  Split class (KFMI_SPLIT): the fetch form the task
@@ -270,6 +334,11 @@ int32_t     kfmi_set_fused(int32_t on);
  * variable.  kfmi_walk_check_last: how the last check decided -- 0 none yet,
  * 1 full, 2 sampled, 3 sampled then full. */
 int32_t     kfmi_set_walk_check(uint32_t mode);
+/* Test knob, process-wide, no environment variable: the next n index uploads
+ * (each attempt of transferCPUtoGPU counts) find no room on the device for
+ * their copy and fail as a full card makes them fail (KFMI_E_DEVICE_ALLOC),
+ * without taking any memory; 0 = none (default). */
+int32_t     kfmi_fail_index_uploads(uint32_t n);
 int32_t     kfmi_walk_check_last(void);
 /* Every entry point leaves the caller's current HIP device as it found it
  * (hipGetDevice before == after), whichever devices it used inside. */

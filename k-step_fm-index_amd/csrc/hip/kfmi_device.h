@@ -131,6 +131,19 @@ struct IdxArgs {
   // own size class, split_for)
   const uint2* __restrict__ skip;
   uint32_t skip_rows, skip_steps, skip_split;
+  // text jump (DESIGN.md 5a''): the full suffix array jsa[row], its inverse
+  // jisa[pos] (bwtsize = n + 1 entries each) and the text's 2-bit codes as the
+  // walk's code stream, jtext -- base n - 1 - g at bits 2g, so the stream that
+  // starts at text position p (base p-1-r at bits 2r) begins at bit
+  // 2 * (n - p); one zero word past the last base.  jsa[row] = SKIP_NONE where
+  // a row holds no suffix.  One allocation, [jsa | jisa | jtext]: jisa =
+  // jsa + bwtsize, jtext = jsa + 2 * bwtsize, so a kernel carries one pointer
+  // (two more cost the 8-word kernel a wave per SIMD).  null = off.  Fused
+  // forward task kernels at K <= 2, plain layouts only.
+  // jump_min: fewest remaining bases a lane jumps with; jump_split: the
+  // gathers into jsa / jisa issued as four 16-lane groups (split_for)
+  const uint32_t* __restrict__ jsa;
+  uint32_t jump_min, jump_split;
 };
 
 constexpr uint32_t SKIP_NONE = 0xFFFFFFFFu;

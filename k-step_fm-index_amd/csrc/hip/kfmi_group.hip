@@ -249,6 +249,7 @@ int32_t group_transfer(kfmi_fmi_t* f, kfmi_qrys_t* q, kfmi_res_t* r, const int* 
           if (hipSetDevice(devs[i]) != hipSuccess) err = KFMI_E_NO_DEVICE;
           if (!err) err = auto_ftab(g->di[i], g->st[i], nullptr);
           if (!err && skip_wanted() == 2u) err = auto_skip(g->di[i], g->st[i]);
+          if (!err && jump_wanted() == 2u) err = auto_jump(g->di[i], g->st[i]);
         }
       if (err) {
         group_free_index(f);
@@ -341,7 +342,7 @@ int32_t group_search(kfmi_fmi_t* f, kfmi_qrys_t* q, kfmi_res_t* r)
   if (gq->n != gi->n || gr->n != gi->n) return KFMI_E_BAD_ARGUMENT;
   for (int i = 0; i < gi->n; ++i)
     if (gq->dev[i] != gi->dev[i] || gr->dev[i] != gi->dev[i] || gq->num[i] != gr->num[i]) return KFMI_E_BAD_ARGUMENT;
-  const uint32_t ftab = ftab_bases(), skip = skip_wanted();
+  const uint32_t ftab = ftab_bases(), skip = tables_wanted();
   int32_t err = KFMI_SUCCESS;
   int queued = 0;
   for (int i = 0; i < gi->n && !err; ++i) {

@@ -214,8 +214,21 @@ __device__ __forceinline__ void fetch_ends_split(const IdxArgs& ix, const uint32
  *   The code words live in LDS after the staging (64 lanes x MAXW words per
  * wave, word-major so a wave's reads of one word index hit 64 banks): `pos`
  * differs per lane, and a register array indexed by it would go to scratch.
- * Lanes only read what they wrote themselves, so no barrier follows. */
-template <class G, int MAXW, int SPLIT>
+ * Lanes only read what they wrote themselves, so no barrier follows.
+ *   JUMP (DESIGN.md 5a'', IdxArgs::jsa): a lane on one row [L, L+1) with at
+ * least jump_min bases left ends its walk with three lookups.  p = jsa[L] is
+ * the one text position that carries the matched suffix, and each of the t
+ * steps left either empties the interval or moves to the row of suffix p - K;
+ * so the walk ends on [jisa[p - tK], + 1) iff p >= tK and the tK text bases
+ * before p are the read's remaining code stream, and empties otherwise.  The
+ * round that would look up the skip table loads jsa[L] instead; a second
+ * round trip, taken only when a lane of the wave jumps, loads the text window
+ * (dwords of jtext, issued together, each lane only its own words) and
+ * jisa[p - tK] -- its address clamped to 0 before the load when p < tK.  A
+ * lane whose compare fails keeps the state it had, never jumps again and goes
+ * on through the skip lookups and K-steps, so it returns the very empty
+ * interval the walk returns. */
+template <class G, int MAXW, int SPLIT, bool JUMP = false>
 __device__ __forceinline__ void skip_walk(const IdxArgs& ix, const uint32_t (&cw)[MAXW], uint32_t steps, uint32_t pos,
                                           uint32_t& Lq, uint32_t& Rq)
 {
@@ -229,13 +242,34 @@ __device__ __forceinline__ void skip_walk(const IdxArgs& ix, const uint32_t (&cw
   const int grp = (int) lane / 16;
   uint32_t L[1] = {Lq}, R[1] = {Rq};
   bool dead = false;   /* a lookup differed: the ordinary steps from here on */
+  /* JUMP: `dead` (bit 0) and "a text jump failed: the skip lookups and steps
+   * from here on" (bit 1) in one VGPR; as two more lane masks they take the
+   * 8-word kernel past 96 SGPRs, a wave per SIMD */
+  uint32_t fl = 0;
+  auto is_dead = [&]() -> bool {
+    if constexpr (JUMP) return (fl & 1u) != 0u;
+    else return dead;
+  };
   while (__ballot(pos < steps)) {
     const bool act = pos < steps;
     const uint32_t bit = pos * (2u * G::K), k = bit >> 5;
     const uint32_t lo = k < (uint32_t) MAXW ? cl[64u * k] : 0u;
     const uint32_t hi = k + 1u < (uint32_t) MAXW ? cl[64u * (k + 1u)] : 0u;
     const uint32_t code = __builtin_amdgcn_alignbit(hi, lo, bit & 31u);   /* the stream from step `pos` on */
-    const bool one = act && !dead && R[0] == L[0] + 1u && L[0] < ix.skip_rows && pos + J <= steps;
+    const bool row1 = act && R[0] == L[0] + 1u;
+    bool jmp = false;
+    uint32_t p = SKIP_NONE;
+    if constexpr (JUMP) {
+      jmp = row1 && !(fl & 2u) && L[0] < ix.bwtsize && (steps - pos) * (uint32_t) G::K >= ix.jump_min;
+      if (ix.jump_split == 4u) {   /* wave-uniform */
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+          if (jmp && grp == g) p = ix.jsa[L[0]];
+      } else if (jmp) {
+        p = ix.jsa[L[0]];
+      }
+    }
+    const bool one = row1 && !jmp && !is_dead() && L[0] < ix.skip_rows && pos + J <= steps;
     uint2 e = make_uint2(SKIP_NONE, 0u);
     if (ix.skip_split == 4u) {   /* wave-uniform: at most 16 pages per gather instruction */
 #pragma unroll
@@ -244,7 +278,7 @@ __device__ __forceinline__ void skip_walk(const IdxArgs& ix, const uint32_t (&cw
     } else if (one) {
       e = ix.skip[L[0]];
     }
-    if (act && !one) {
+    if (act && !one && !jmp) {
       uint32_t c[1] = {code & (uint32_t) (G::NC - 1)};
       uint32_t sx[2 * G::K];
       plane_xor<G::K>(c[0], sx);
@@ -265,7 +299,52 @@ __device__ __forceinline__ void skip_walk(const IdxArgs& ix, const uint32_t (&cw
         R[0] = e.x + 1u;
         pos += J;
       } else {
-        dead = true;
+        if constexpr (JUMP) fl |= 1u;
+        else dead = true;
+      }
+    }
+    if constexpr (JUMP) {
+      if (__ballot(jmp)) {   /* wave-uniform: the text window and the ISA entry, one more round trip */
+        const uint32_t nb = (steps - pos) * (uint32_t) G::K;          /* bases left: the window */
+        const bool ok = jmp && p < ix.bwtsize && p >= nb;             /* SKIP_NONE fails the first test */
+        const uint32_t q = ok ? p - nb : 0u;                          /* in range before the load is issued */
+        const uint32_t off = ok ? ix.bwtsize - 1u - p : 0u;                /* the stream at p starts at bit 2 * off */
+        const uint32_t tw = off >> 4, tsh = (off & 15u) * 2u;
+        const uint32_t nw = ok ? (nb + 15u) >> 4 : 0u;                /* words compared, <= MAXW */
+        uint32_t tx[MAXW + 1];
+#pragma unroll
+        for (int j = 0; j <= MAXW; ++j) {
+          tx[j] = 0u;
+          if (ok && (uint32_t) j <= nw) tx[j] = ix.jsa[2ull * ix.bwtsize + tw + (uint32_t) j];
+        }
+        uint32_t r = SKIP_NONE;
+        if (ix.jump_split == 4u) {   /* wave-uniform */
+#pragma unroll
+          for (int g = 0; g < 4; ++g)
+            if (ok && grp == g) r = ix.jsa[(uint64_t) ix.bwtsize + q];
+        } else if (ok) {
+          r = ix.jsa[(uint64_t) ix.bwtsize + q];
+        }
+        uint32_t diff = 0u;
+#pragma unroll
+        for (int j = 0; j < MAXW; ++j) {
+          if ((uint32_t) j < nw) {
+            const uint32_t kj = k + (uint32_t) j;
+            const uint32_t rl = kj < (uint32_t) MAXW ? cl[64u * kj] : 0u;
+            const uint32_t rh = kj + 1u < (uint32_t) MAXW ? cl[64u * (kj + 1u)] : 0u;
+            const uint32_t rw = __builtin_amdgcn_alignbit(rh, rl, bit & 31u);
+            const uint32_t tv = __builtin_amdgcn_alignbit(tx[j + 1], tx[j], tsh);
+            const uint32_t left = 2u * nb - 32u * (uint32_t) j;   /* bits of the window from this word on */
+            diff |= (rw ^ tv) & (left >= 32u ? 0xFFFFFFFFu : (1u << left) - 1u);
+          }
+        }
+        if (ok && diff == 0u && r < ix.bwtsize) {
+          L[0] = r;
+          R[0] = r + 1u;
+          pos = steps;
+        } else if (jmp) {
+          fl |= 2u;
+        }
       }
     }
   }
@@ -396,8 +475,10 @@ __device__ __forceinline__ void seed_walk(const IdxArgs& ix, const uint32_t (&cw
 }
 
 /* SKIP (last template value, fused K <= 2 only): the walk with the skip table,
- * launched when ix.skip is set; without it the kernel is the plain walk. */
-template <class G, int QPT, int MAXW, int SPLIT = 1, bool SKIP = false>
+ * launched when ix.skip or ix.jsa is set; without it the kernel is the plain
+ * walk.  JUMP (with SKIP, plain layouts): skip_walk with the text jump, launched
+ * when ix.jsa is set; the strand and words kernels are compiled without it. */
+template <class G, int QPT, int MAXW, int SPLIT = 1, bool SKIP = false, bool JUMP = false>
 __global__ __launch_bounds__(256) void task_kernel(IdxArgs ix, const uint32_t* __restrict__ qp,
                                                    const uint8_t* __restrict__ ascii, uint32_t m, uint64_t num,
                                                    uint32_t steps, uint32_t nwords, uint32_t* __restrict__ res)
@@ -406,6 +487,7 @@ __global__ __launch_bounds__(256) void task_kernel(IdxArgs ix, const uint32_t* _
   constexpr int CW = MAXW > 0 ? (G::K == 3 ? k3_words<(MAXW > 0 ? MAXW : 1)>() : MAXW) : 1;
   static_assert(MAXW == 0 || QPT == 1, "fused packing: one query per thread");
   static_assert(!SKIP || (MAXW > 0 && G::K <= 2), "skip table: fused task kernels at K <= 2");
+  static_assert(!JUMP || (SKIP && (G::LAY == LAY_INTER || G::LAY == LAY_MID)), "text jump: skip_walk, plain layouts");
   const uint64_t base = (uint64_t) blockIdx.x * (256 * QPT) + threadIdx.x;
   uint32_t cw[QPT][CW];
   uint32_t rc = 0;
@@ -451,7 +533,7 @@ __global__ __launch_bounds__(256) void task_kernel(IdxArgs ix, const uint32_t* _
     }
   }
   if constexpr (SKIP) {
-    skip_walk<G, MAXW, SPLIT>(ix, cw[0], steps, skip, L[0], R[0]);
+    skip_walk<G, MAXW, SPLIT, JUMP>(ix, cw[0], steps, skip, L[0], R[0]);
     *reinterpret_cast<uint2*>(res + 2 * base) = make_uint2(L[0], R[0]);
     return;
   }
@@ -745,6 +827,44 @@ __global__ __launch_bounds__(256) void skip_level0_kernel(IdxArgs ix, uint64_t r
   }
 }
 
+/* Text jump, the code stream of the text (DESIGN.md 5a'', IdxArgs::jtext): one
+ * thread per word.  Word w holds the 16 bases before text position
+ * p0 = n - 16w, base p0-1-r at bits 2r; they are the K-mer codes of the rows
+ * of suffixes p0, p0 - K, ... (row_code: base p-1-s at bits 2s), found through
+ * isa -- consecutive words read isa 16 entries apart, one index line per K
+ * bases, whole words stored.  Bases before position 0 and the words past the
+ * text are zero.  With `split` the index gather goes out as four 16-lane
+ * groups, like the task kernels' (the rows are random in the index). */
+template <class G>
+__global__ __launch_bounds__(256) void jump_text_kernel(IdxArgs ix, const uint32_t* __restrict__ isa, uint64_t n,
+                                                        uint64_t words, uint32_t split, uint32_t* __restrict__ out)
+{
+  const int grp = (int) (threadIdx.x & 63) / 16;
+  for (uint64_t w0 = (uint64_t) blockIdx.x * 256 + (threadIdx.x & ~63u); w0 < words; w0 += (uint64_t) gridDim.x * 256) {
+    const uint64_t w = w0 + (threadIdx.x & 63u);
+    uint32_t v = 0;
+#pragma unroll 1
+    for (uint32_t u = 0; u < 16u / (uint32_t) G::K; ++u) {
+      const uint64_t back = 16ull * w + (uint64_t) u * G::K;   /* p = n - back */
+      const bool on = w < words && back < n;                    /* p >= 1: base p-1 exists */
+      const uint64_t p = on ? n - back : 0;
+      const uint32_t row = on ? isa[p] : 0u;
+      const bool ok = on && row < ix.bwtsize;
+      uint32_t c = 0;
+      if (split) {   /* wave-uniform */
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+          if (ok && grp == g) c = row_code<G>(ix, row);
+      } else if (ok) {
+        c = row_code<G>(ix, row);
+      }
+      if (p < (uint64_t) G::K) c &= (1u << (2u * (uint32_t) p)) - 1u;   /* only bases p-1 .. 0 are text */
+      v |= c << (2u * (uint32_t) G::K * u);
+    }
+    if (w < words) out[w] = v;
+  }
+}
+
 /* Remainder table for reads with m % K = rem (1 <= rem < K): [L, R) of every
  * rem-base string x (base m-1 at bits 0-1, the code order of the K-steps).
  * A K-step from [0, n+1) gives the suffix-array range of a K-mer, so
@@ -997,6 +1117,11 @@ struct SearchLaunch {
   /* walk check (Op::PermCheck): every row's LF_K successor, and the flag of an image past the rows */
   uint32_t* perm_next;
   uint32_t* perm_bad;
+  /* text jump, the code stream (Op::JumpText): num = n bases through jump_isa -> jump_words words of jump_text */
+  const uint32_t* jump_isa;
+  uint32_t* jump_text;
+  uint64_t jump_words;
+  uint32_t jump_split;
 };
 
 template <class G, int SPLIT>
@@ -1019,8 +1144,19 @@ static void launch_task_split(const SearchLaunch& a)
     }
     const uint64_t blocks = (a.num + 255) / 256;
     if constexpr (G::K <= 2) {
-      if (a.ix.skip) {   /* the walk with the skip table; LDS: the staging, then 64 x maxw code words per wave */
+      if (a.ix.skip || a.ix.jsa) {   /* the walk with the tables; LDS: the staging, then 64 x maxw code words per wave */
         const size_t lds_skip = std::max(lds, (size_t) 4 * 64 * 4 * (size_t) a.maxw);
+        if constexpr (G::LAY == LAY_INTER || G::LAY == LAY_MID) {
+          if (a.ix.jsa) {   /* with the text jump (DESIGN.md 5a'') */
+            if (a.maxw == 8)
+              hipLaunchKernelGGL((task_kernel<G, 1, 8, SPLIT, true, true>), dim3((uint32_t) blocks), dim3(256), lds_skip,
+                                 a.st, a.ix, a.qp, a.ascii, a.m, a.num, a.steps, a.nwords, a.res);
+            else
+              hipLaunchKernelGGL((task_kernel<G, 1, 16, SPLIT, true, true>), dim3((uint32_t) blocks), dim3(256), lds_skip,
+                                 a.st, a.ix, a.qp, a.ascii, a.m, a.num, a.steps, a.nwords, a.res);
+            return;
+          }
+        }
         if (a.maxw == 8)
           hipLaunchKernelGGL((task_kernel<G, 1, 8, SPLIT, true>), dim3((uint32_t) blocks), dim3(256), lds_skip, a.st,
                              a.ix, a.qp, a.ascii, a.m, a.num, a.steps, a.nwords, a.res);
@@ -1247,7 +1383,18 @@ static hipError_t launch_perm(const SearchLaunch& a)
   return hipGetLastError();
 }
 
-enum class Op { Task, Coop, Count, Locate, Ftab, RemTab, CountLines, Derive, PermCheck, Skip0 };
+template <class G>
+static hipError_t launch_jump_text(const SearchLaunch& a)
+{
+  if constexpr (G::K <= 2 && (G::LAY == LAY_INTER || G::LAY == LAY_MID)) {
+    hipLaunchKernelGGL((jump_text_kernel<G>), dim3(grid_blocks((a.jump_words + 255) / 256, 1u << 20)), dim3(256), 0, a.st,
+                       a.ix, a.jump_isa, a.num, a.jump_words, a.jump_split, a.jump_text);
+    return hipGetLastError();
+  }
+  return hipErrorInvalidValue;
+}
+
+enum class Op { Task, Coop, Count, Locate, Ftab, RemTab, CountLines, Derive, PermCheck, Skip0, JumpText };
 
 /* Defined here, instantiated once per (K, NB, LAY) in kfmi_inst_*.hip. */
 template <int K, int NB, int LAY>
@@ -1264,6 +1411,7 @@ hipError_t dispatch_one(Op op, const SearchLaunch& a, unsigned long long* d_tota
     case Op::Derive: return launch_derive<G>(a);
     case Op::PermCheck: return launch_perm<G>(a);
     case Op::Skip0: return launch_skip0<G>(a);
+    case Op::JumpText: return launch_jump_text<G>(a);
     default: return launch_count<G>(a, d_total);
   }
 }

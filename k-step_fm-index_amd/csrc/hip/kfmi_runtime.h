@@ -60,6 +60,14 @@ struct kfmi_dev_index {
    * decision of this copy (auto_skip): -1 not yet, 0 none, 1 built */
   uint2* skip = nullptr;
   int skip_auto = -1;
+  /* text jump (DESIGN.md 5a'', kfmi_jump.hip): one allocation [sa | isa | text],
+   * bwtsize + bwtsize + (n / 16 + 2) words; K <= 2, task backends on the plain
+   * layouts; same lifetime rule and mutex as the ftabs.  jump_auto: the auto
+   * decision of this copy (auto_jump): -1 not yet, 0 none, 1 built; jump_none:
+   * the index failed the build's exactness check, so it never gets tables */
+  uint32_t* jump_sa = nullptr;
+  int jump_auto = -1;
+  int jump_none = 0;
   /* remainder tables: [L, R) of every r-base read suffix, r = m % K in 1..3
    * (same lifetime rule as the ftabs, same mutex) */
   uint2* rtab[4] = {};
@@ -156,6 +164,22 @@ void drop_ftabs(kfmi_dev_index* di);
  * the caller's skip_wanted() */
 int32_t auto_skip(kfmi_dev_index* di, hipStream_t st);
 int32_t use_skip(kfmi_dev_index* di, hipStream_t st, IdxArgs& ix, uint32_t want);
+/* the text jump (kfmi_jump.hip): the caller's setting (0 off, 1 on, 2 auto and
+ * in effect: exactly when skip_wanted() is 2), the auto tables of a device copy
+ * (never an error when they do not fit or the index fails the check), ix.jsa
+ * for a search, and the tables' release (caller holds ftab_mu or the handle's
+ * exclusive lock).  A search's `skip` argument carries both settings:
+ * tables_wanted() = skip_wanted() | jump_wanted() << 4, taken apart by use_skip;
+ * the strand and seed searches pass skip_wanted() alone and never jump. */
+uint32_t jump_wanted(void);
+inline uint32_t tables_wanted(void) { return skip_wanted() | (jump_wanted() << 4); }
+int32_t auto_jump(kfmi_dev_index* di, hipStream_t st);
+int32_t use_jump(kfmi_dev_index* di, hipStream_t st, IdxArgs& ix, uint32_t want);
+void free_jump(kfmi_dev_index* di);
+/* per-lane gathers of a table of this size as lane groups: 4, 2 or 1 (KFMI_SPLIT answers instead) */
+uint32_t split_for(uint64_t table_bytes, int layout);
+/* the tables' budget now: kfmi_set_ftab_budget's bytes, or a quarter of the free memory of the current device */
+uint64_t table_budget_now(void);
 /* reads with m % K = rem != 0: layouts that take the remainder
  * table, and the table of an index (built on first use; clears the ftab) */
 bool rem_supported(int layout);

@@ -797,6 +797,7 @@ void free_dev_index(kfmi_dev_index* di)
   for (uint2* t : di->ftab)
     if (t) (void) hipFree(t);
   if (di->skip) (void) hipFree(di->skip);
+  free_jump(di);
   for (uint2* t : di->rtab)
     if (t) (void) hipFree(t);
   delete di;
@@ -907,6 +908,29 @@ int32_t upload_sa(const kfmi_fmi_t* f, kfmi_dev_index* di, DevCtx* ctx)
   return KFMI_SUCCESS;
 }
 
+/* Test knob (kstep_fmi.h kfmi_fail_index_uploads): the next `n` index uploads
+ * find no room for their copy.  The refusal is a real one -- a hipMalloc of
+ * 2^60 bytes, which fails at once and takes no memory -- so the runtime's last
+ * error is what a full card leaves behind. */
+static std::atomic<uint32_t> g_upload_fail{0};
+
+extern "C" int32_t kfmi_fail_index_uploads(uint32_t n)
+{
+  g_upload_fail.store(n, std::memory_order_relaxed);
+  return KFMI_SUCCESS;
+}
+
+static bool upload_refused()
+{
+  uint32_t n = g_upload_fail.load(std::memory_order_relaxed);
+  while (n && !g_upload_fail.compare_exchange_weak(n, n - 1, std::memory_order_relaxed)) {
+  }
+  if (!n) return false;
+  void* p = nullptr;
+  if (hipMalloc(&p, 1ull << 60) == hipSuccess) (void) hipFree(p);   /* never: no device has an exbibyte */
+  return true;
+}
+
 /* Uploads f for `backend` to `dev`: into f->dev, or into *out (group replicas). */
 int32_t upload_index(kfmi_fmi_t* f, int backend, int dev, DevCtx* ctx, kfmi_dev_index** out)
 {
@@ -985,6 +1009,7 @@ int32_t upload_index(kfmi_fmi_t* f, int backend, int dev, DevCtx* ctx, kfmi_dev_
     return code;
   };
 
+  if (upload_refused()) return fail(KFMI_E_DEVICE_ALLOC);
   if (lay == LAY_INTER || lay == LAY_AC) {
     /* entries + 2 padding entries (B5 guard; AC may look at b+1 of the sentinel) */
     di->ent_bytes = body + 4ull * ew * 2;
@@ -1123,7 +1148,7 @@ static void warn_stale_knobs_once()
   });
 }
 
-static uint32_t split_for(uint64_t table_bytes, int layout)
+uint32_t split_for(uint64_t table_bytes, int layout)
 {
   warn_stale_knobs_once();
   const int cls = knob_once(g_split_class, split_class_from_env);
@@ -1159,6 +1184,9 @@ IdxArgs idx_args(const kfmi_dev_index* di)
   ix.skip_rows = 0;
   ix.skip_steps = 0;
   ix.skip_split = 1;
+  ix.jsa = nullptr;
+  ix.jump_min = 0xFFFFFFFFu;
+  ix.jump_split = 1;
   return ix;
 }
 
@@ -1629,6 +1657,20 @@ static bool skip_applies(const kfmi_dev_index* di)
   return di->K >= 1 && di->K <= 2 && !is_coop(di->backend) && di->layout != LAY_GRP;
 }
 
+uint64_t table_budget_now(void)
+{
+  uint64_t budget = g_ftab_budget.load(std::memory_order_relaxed);
+  if (budget == KFMI_FTAB_BUDGET_FREE) {
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
+      (void) hipGetLastError();
+      free_b = 0;
+    }
+    budget = (uint64_t) free_b / 4;
+  }
+  return budget;
+}
+
 /* The auto skip table of an index, decided once per device copy after its auto
  * ftab: built when kfmi_skip_auto says the table and its transient twin fit the
  * budget -- a quarter of the device memory free right now, or
@@ -1661,6 +1703,9 @@ int32_t auto_skip(kfmi_dev_index* di, hipStream_t st)
  * under another setting), 1 = built now if it is not there. */
 int32_t use_skip(kfmi_dev_index* di, hipStream_t st, IdxArgs& ix, uint32_t want)
 {
+  const int32_t ej = use_jump(di, st, ix, want >> 4);   /* tables_wanted(): the text jump's setting rides above */
+  if (ej) return ej;
+  want &= 15u;
   ix.skip = nullptr;
   ix.skip_rows = 0;
   ix.skip_steps = 0;
@@ -1690,7 +1735,8 @@ int32_t use_skip(kfmi_dev_index* di, hipStream_t st, IdxArgs& ix, uint32_t want)
  * derived data, up to 34 GB each, and the replacing upload needs the memory:
  * a K = 4 copy re-laid for another backend holds two 96 GB layouts for a
  * moment.  Should that upload fail, the old copy stays searchable and builds
- * its tables again on demand. */
+ * its tables again on demand -- except when it fails for lack of device
+ * memory: then transferCPUtoGPU frees the old copy too and uploads again. */
 void drop_ftabs(kfmi_dev_index* di)
 {
   if (!di) return;
@@ -1705,6 +1751,7 @@ void drop_ftabs(kfmi_dev_index* di)
   if (di->skip) (void) hipFree(di->skip);   /* the skip table goes with them */
   di->skip = nullptr;
   di->skip_auto = -1;
+  free_jump(di);   /* and the text jump's */
 }
 
 /* The ftab of `bases` bases (KFMI_FTAB_AUTO: the index's auto table), built
@@ -1953,9 +2000,23 @@ extern "C" int32_t transferCPUtoGPU(void* index, void* queries, void* results)
         drop_ftabs(f->dev);    /* the copy being replaced: its tables' memory goes to the new one */
         (void) hipSetDevice(dev);
         err = upload_index(f, backend, dev, ctx);
+        if (err == KFMI_E_DEVICE_ALLOC && f->dev) {
+          /* no room for the old copy and the new one together (a K = 4 layout is
+           * 96 GB, and other handles' tables share the card): the old copy goes
+           * first, under the exclusive lock already held, and the upload runs again */
+          (void) hipGetLastError();
+          free_dev_index(f->dev);
+          f->dev = nullptr;
+          (void) hipSetDevice(dev);
+          err = upload_index(f, backend, dev, ctx);
+        }
+        /* a failed hipMalloc stays in the runtime's last error: left there, the next upload's
+         * first launch check would read it as its own */
+        if (err == KFMI_E_DEVICE_ALLOC) (void) hipGetLastError();
         /* the auto jump-start table is part of the upload, like the re-layout */
         if (!err && ftab_bases() == KFMI_FTAB_AUTO) err = auto_ftab(f->dev, ctx->st, nullptr);
         if (!err && skip_wanted() == 2u) err = auto_skip(f->dev, ctx->st);   /* and the skip table after it */
+        if (!err && jump_wanted() == 2u) err = auto_jump(f->dev, ctx->st);   /* then the text jump's tables */
         if (err) return err;
       }
       qk = device_steps(f);
@@ -2059,7 +2120,7 @@ extern "C" int32_t kfmi_search(void* index, void* queries, void* results)
   hipEvent_t* ev = err ? nullptr : thread_events(di->device);
   hipStream_t st = err ? nullptr : thread_stream(di->device);
   if (!err && (!ev || !st)) err = KFMI_E_NO_DEVICE;
-  if (!err) err = search_enqueue(di, q->dev, r->d_results, st, ev, ftab_bases(), skip_wanted());
+  if (!err) err = search_enqueue(di, q->dev, r->d_results, st, ev, ftab_bases(), tables_wanted());
   if (!err) err = search_finish(st, ev, t_ms);
   return err;
 }

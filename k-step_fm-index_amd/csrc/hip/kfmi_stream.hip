@@ -563,7 +563,7 @@ extern "C" int32_t kfmi_search_stream_strands(void* index, const char* ascii, ui
   double ms[KFMI_MAX_GROUP][3] = {};
   uint64_t np[KFMI_MAX_GROUP] = {};
   int32_t err = KFMI_SUCCESS;
-  const uint32_t ftab = ftab_bases(), skip = skip_wanted();
+  const uint32_t ftab = ftab_bases(), skip = strands == KFMI_STRAND_FWD ? tables_wanted() : skip_wanted();
   if (!g) {
     err = stream_on(f->dev, 0, ascii, num, size, results, chunk, ftab, skip, ms[0], &np[0], strands);
   } else {

@@ -126,8 +126,16 @@ def load() -> ctypes.CDLL:
         "kfmi_skip_auto": (u32, [u64, u32, u64]),
         "kfmi_device_skip_bytes": (u64, [vp]),
         "kfmi_device_skip_table": (i32, [vp, vp, u64, ctypes.POINTER(u32)]),
+        "kfmi_set_jump": (i32, [u32]),
+        "kfmi_jump_in_effect": (u32, []),
+        "kfmi_set_jump_min": (i32, [u32]),
+        "kfmi_jump_min": (u32, []),
+        "kfmi_jump_auto": (u32, [u64, u32, u64]),
+        "kfmi_device_jump_bytes": (u64, [vp]),
+        "kfmi_device_jump_tables": (i32, [vp, u32, vp, vp, u64, vp, u64]),
         "kfmi_set_fused": (i32, [i32]),
         "kfmi_set_walk_check": (i32, [u32]),
+        "kfmi_fail_index_uploads": (i32, [u32]),
         "kfmi_walk_check_last": (i32, []),
         "kfmi_set_alphabet": (i32, [ctypes.c_char_p]),
         "kfmi_index_sa": (i32, [vp, pvp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]),
@@ -217,6 +225,38 @@ def skip_auto(rows: int, k: int, budget_bytes: int) -> bool:
     return bool(load().kfmi_skip_auto(int(rows), int(k), int(budget_bytes)))
 
 
+JUMP_AUTO = 0xFFFFFFFF
+JUMP_MIN_DEFAULT = 8
+
+
+def set_jump(mode) -> None:
+    """Text jump: 0 = off, 1 = on, "auto" (the default) = in effect exactly
+    when the skip setting is auto and in effect; per calling thread."""
+    n = JUMP_AUTO if mode == "auto" else int(mode)
+    _check(load().kfmi_set_jump(n), f"set_jump({mode})")
+
+
+def jump_in_effect() -> int:
+    """The calling thread's jump setting resolved against its skip setting:
+    0 = off, 1 = on (explicit), 2 = auto and in effect."""
+    return int(load().kfmi_jump_in_effect())
+
+
+def set_jump_min(bases: int) -> None:
+    """Fewest remaining bases a lane jumps with (process-wide; default 8)."""
+    _check(load().kfmi_set_jump_min(int(bases)), f"set_jump_min({bases})")
+
+
+def jump_min() -> int:
+    return int(load().kfmi_jump_min())
+
+
+def jump_auto(rows: int, k: int, budget_bytes: int) -> bool:
+    """The auto rule: whether an index of `rows` (n + 1) rows and K = k gets
+    the text jump's tables within `budget_bytes`."""
+    return bool(load().kfmi_jump_auto(int(rows), int(k), int(budget_bytes)))
+
+
 def set_split_class(cls: int) -> None:
     """Fetch form of the task kernels by table-size class (0 = by the uploaded
     table's size, 1 / 2 / 4 = that class); process-wide test knob (KFMI_SPLIT)."""
@@ -227,6 +267,11 @@ def set_fused(on: bool) -> None:
     """In-kernel query packing where it fits (True, default) or always the
     separate pack launch (False); process-wide test knob (KFMI_FUSED)."""
     _check(load().kfmi_set_fused(1 if on else 0), f"set_fused({on})")
+
+
+def fail_index_uploads(n: int) -> None:
+    """Test knob: the next n index uploads fail for lack of device memory (0 = none)."""
+    _check(load().kfmi_fail_index_uploads(int(n)), f"fail_index_uploads({n})")
 
 
 def set_walk_check(mode: int) -> None:
@@ -419,6 +464,24 @@ class Index(_Handle):
     def skip_bytes(self) -> int:
         """Bytes of the skip tables beside the device copies (not in device_bytes / ftab_bytes)."""
         return int(load().kfmi_device_skip_bytes(self._p))
+
+    def jump_bytes(self) -> int:
+        """Bytes of the text jump's tables beside the device copies (all members of a group)."""
+        return int(load().kfmi_device_jump_bytes(self._p))
+
+    def jump_tables(self, member: int = 0):
+        """Test accessor: (sa, isa, text) of the single-device copy or of a
+        group member: uint32 [rows], uint32 [rows], uint32 [n // 16 + 2] (base
+        n - 1 - g of the text at bits 2g of the word stream)."""
+        rows = int(self.header()["bwtsize"])
+        words = (rows - 1) // 16 + 2
+        sa = np.empty(rows, dtype=np.uint32)
+        isa = np.empty(rows, dtype=np.uint32)
+        text = np.empty(words, dtype=np.uint32)
+        as_p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        _check(load().kfmi_device_jump_tables(self._p, int(member), as_p(sa), as_p(isa), rows, as_p(text), words),
+               "jump_tables")
+        return sa, isa, text
 
     def skip_table(self):
         """Test accessor: (J, uint32 [rows, 2] of {row, code}) of the single-device copy's skip table."""
