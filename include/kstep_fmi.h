@@ -288,8 +288,27 @@ int32_t     kfmi_device_skip_table(void *index, void *out, uint64_t entries, uin
  * a device group) when kfmi_jump_auto() allows it, and a failed allocation
  * leaves them out, never an error; 1 = on whatever the other settings: built
  * at the first search, KFMI_E_DEVICE_ALLOC when they do not fit.  Freed with
- * the jump-start tables.  Default footprint of an uploaded 3 Gbase index with
- * every auto table: about 86 GB (3 index + 34 ftab + 24 skip + 24.75). */
+ * the jump-start tables.
+ *   Line table (DESIGN.md 5a'''): behind the three tables, in the same
+ * allocation, 128-byte lines of 16 ISA entries and the 256 text bases that end
+ * where those entries' windows end, so a window of up to 240 bases and its ISA
+ * entry cost one memory line instead of two or three.  n / 16 + 2 lines, 8 B x
+ * rows and a little: 24 GB at 3 Gbase.  They take the place the build's
+ * temporary arrays had, so the build's peak is what it was.  Longer windows
+ * use the flat tables.  kfmi_set_jump_lines / KFMI_JUMP_LINES (process-wide, a
+ * search reads it when it is queued; default 1): 0 = every window from the
+ * flat tables, 1 = from the lines, every load of that round trip issued per
+ * 16-lane group where the tables are past the translation reach (as the other
+ * gathers are), 2 = from the lines with the window's loads never split (the
+ * slower form, kept for measurements: 1.21 against 1.00 ms per 10M 100 bp
+ * reads at 3 Gbase, DESIGN.md 5a'''); the lines are built either way and no
+ * setting changes a result.  Read-length rule: where the loads go out per
+ * 16-lane group (tables past the translation reach, 3 Gbase), a search of
+ * reads longer than 192 bases takes the flat tables' form under setting 1 as
+ * well -- from about 196 bases on the grouped loads cost more than the saved
+ * line (jump_sweep_r12*.jsonl, DESIGN.md 5a''').
+ *   Default footprint of an uploaded 3 Gbase index with every auto table:
+ * about 110 GB (3 index + 34 ftab + 24 skip + 24.75 + 24 lines). */
 #define KFMI_JUMP_AUTO 0xFFFFFFFFu
 #define KFMI_JUMP_MIN_DEFAULT 8u
 int32_t     kfmi_set_jump(uint32_t mode);
@@ -315,6 +334,25 @@ uint64_t    kfmi_device_jump_bytes(void *index);
  * past the text.  KFMI_E_NOT_ON_DEVICE without tables. */
 int32_t     kfmi_device_jump_tables(void *index, uint32_t member, uint32_t *sa, uint32_t *isa, uint64_t rows,
                                     uint32_t *text, uint64_t words);
+/* The line table's use by the search (above), and the value in effect. */
+int32_t     kfmi_set_jump_lines(uint32_t mode);
+uint32_t    kfmi_jump_lines(void);
+/* Bytes of the line tables the handle's device copies hold (all members of a
+ * device group), not counted in kfmi_device_jump_bytes: 128 * (n / 16 + 2) per
+ * copy. */
+uint64_t    kfmi_device_jump_line_bytes(void *index);
+/* Test accessor: the raw lines of the same copy as kfmi_device_jump_tables,
+ * out[32 * lines], lines = n / 16 + 2 (the last one padding).  Line j: dword
+ * t < 16 = isa[n - (16 j + t)], 0xFFFFFFFF where 16 j + t > n; dwords 16 .. 31
+ * = words j - 15 .. j of the text's word stream, zero outside it. */
+int32_t     kfmi_device_jump_lines(void *index, uint32_t member, uint32_t *out, uint64_t lines);
+/* Host arithmetic of a lane's reads in the line table, for the tests: out[0] =
+ * the lines' first dword in the allocation, out[1] = the line count, and for a
+ * jump with nb <= 240 bases left at text position p (nb <= p <= n), as dwords
+ * from the lines' start: out[2] = its ISA entry, out[3] = the first dword of
+ * its window, out[4] = the window's bit offset there, out[5] = the dwords the
+ * compare reads. */
+int32_t     kfmi_jump_line_geometry(uint64_t n, uint64_t p, uint32_t nb, uint64_t *out);
 /* Test knobs of the search path (not in the reference), process-wide; their
  * environment variables are read once, at the first search, and these setters
  * switch them afterwards.  Split class (KFMI_SPLIT): the fetch form the task

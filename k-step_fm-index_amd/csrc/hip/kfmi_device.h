@@ -141,12 +141,62 @@ struct IdxArgs {
   // (two more cost the 8-word kernel a wave per SIMD).  null = off.  Fused
   // forward task kernels at K <= 2, plain layouts only.
   // jump_min: fewest remaining bases a lane jumps with; jump_split: the
-  // gathers into jsa / jisa issued as four 16-lane groups (split_for)
+  // gathers into jsa / jisa issued as four 16-lane groups (bit JUMP_SPLIT4,
+  // split_for), and the forms of the line table below (bits JUMP_LINES,
+  // JUMP_LINES_GROUPED) -- one argument, so the switches cost no scalar
+  // register.
+  // Line table (DESIGN.md 5a'''): behind jtext, from dword jump_lines_off(
+  // bwtsize) on, 128-byte lines of JUMP_LINE_S ISA entries and the 256 text
+  // bases that end where those entries' windows end.  With e = n - p + nb the
+  // end of a jump's window in jtext's slots (nb bases left at text position
+  // p), line e / S holds isa[n - e] in dword e % S and the stream slots
+  // [S * (e / S) + S - 256, S * (e / S) + S) in dwords 16 .. 31, lowest slot
+  // at bit 0 of dword 16; SKIP_NONE where e > n, zero bases outside the text.
+  // Every window of nb <= JUMP_LINE_W bases lies inside its line.
   const uint32_t* __restrict__ jsa;
   uint32_t jump_min, jump_split;
 };
 
 constexpr uint32_t SKIP_NONE = 0xFFFFFFFFu;
+
+// The text jump's line table: ISA entries per line, the longest window a line
+// serves (256 - S bases), dwords per line and the line's first text dword.
+constexpr uint32_t JUMP_LINE_S = 16, JUMP_LINE_W = 256 - JUMP_LINE_S, JUMP_LINE_DW = 32, JUMP_LINE_TEXT = JUMP_LINE_S;
+static_assert(JUMP_LINE_S == 16 && JUMP_LINE_S + 256 / 16 == JUMP_LINE_DW, "a line: S entries, then 256 bases in 16 dwords");
+// IdxArgs::jump_split
+constexpr uint32_t JUMP_SPLIT4 = 4u, JUMP_LINES = 0x100u, JUMP_LINES_GROUPED = 0x200u;
+// Longest read whose launch takes the lines in the grouped form: four groups
+// of up to 17 loads cost more issue slots than the saved line is worth from
+// about 196 bases on (3 Gbase: profiles/r12/jump_sweep_r12*.jsonl, the table
+// in DESIGN.md 5a'''); longer reads are launched with the flat tables' form.
+constexpr uint32_t JUMP_LINES_GROUPED_MAX_M = 192;
+
+// words of the code stream of an n-base text: its bases, then at least one zero word
+__host__ __device__ constexpr uint64_t jump_text_words(uint64_t n) { return n / 16 + 2; }
+// lines of an n-base text: one per S window ends e = 0 .. n, and one of padding
+__host__ __device__ constexpr uint64_t jump_line_count(uint64_t n) { return n / JUMP_LINE_S + 2; }
+// first dword of the lines in [sa | isa | text | lines]: behind the text, on a 128-byte boundary
+__host__ __device__ constexpr uint64_t jump_lines_off(uint64_t rows)
+{
+  return (2 * rows + jump_text_words(rows - 1) + (JUMP_LINE_DW - 1)) & ~(uint64_t) (JUMP_LINE_DW - 1);
+}
+
+// Where a jump with nb bases left at text position p (nb <= p <= n) reads in
+// the line table, as dwords from the lines' start: its ISA entry, the first
+// dword of its window, the window's bit offset in that dword, and how many
+// dwords the compare needs -- none of them outside the lane's own line.
+struct JumpLineAt {
+  uint64_t isa_dw, text_dw;
+  uint32_t shift, ndw;
+};
+__host__ __device__ constexpr JumpLineAt jump_line_at(uint32_t n, uint32_t p, uint32_t nb)
+{
+  const uint32_t e = n - p + nb, j = e / JUMP_LINE_S;
+  const uint32_t s = 256u - JUMP_LINE_S + e % JUMP_LINE_S - nb;   /* the window's first slot in the line's text half */
+  const uint64_t line = (uint64_t) j * JUMP_LINE_DW;
+  return JumpLineAt{line + e % JUMP_LINE_S, line + JUMP_LINE_TEXT + (s >> 4), (s & 15u) * 2u,
+                    ((s + nb + 15u) >> 4) - (s >> 4)};
+}
 
 typedef unsigned int v4u __attribute__((ext_vector_type(4)));
 typedef unsigned int v2u __attribute__((ext_vector_type(2)));

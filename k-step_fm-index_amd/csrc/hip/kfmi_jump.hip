@@ -13,7 +13,10 @@
  * (dist = 1 on ordinary rows, 0 on '$' rows), ceil(log2 rows) rounds between
  * two pairs of 4-byte arrays.  Then sa is written over the last pointers,
  * isa[sa[i]] = i over their spent twin, and the code stream is filled through
- * isa (jump_text_kernel).  Peak: 8 B x rows beside the finished tables.
+ * isa (jump_text_kernel).  The distances live where the line table (DESIGN.md
+ * 5a''') goes: its 128-byte lines are 8 B x rows and a little, and they are
+ * filled last, from isa and the code stream (jump_lines_kernel), when the
+ * distances are spent -- so the build allocates nothing that goes.
  *
  * Exactness is checked, not assumed: the tables are kept only when every
  * chain ends at a '$' row, every sa value is a text position (<= n) and every
@@ -42,6 +45,7 @@ namespace kfmi {
 
 static thread_local int t_jump = -1;   /* -1: KFMI_JUMP, else auto; 0 off, 1 on, 2: auto (kfmi_set_jump) */
 static std::atomic<uint32_t> g_jump_min{KFMI_JUMP_MIN_DEFAULT};
+static std::atomic<int> g_jump_lines{-1};   /* -1: KFMI_JUMP_LINES, else 1; kfmi_set_jump_lines */
 
 extern "C" int32_t kfmi_set_jump(uint32_t mode)
 {
@@ -79,8 +83,51 @@ extern "C" int32_t kfmi_set_jump_min(uint32_t bases)
 
 extern "C" uint32_t kfmi_jump_min(void) { return g_jump_min.load(std::memory_order_relaxed); }
 
-/* words of the code stream of an n-base text: its bases, then at least one zero word */
-static uint64_t text_words(uint64_t n) { return n / 16 + 2; }
+/* The line table's use by the search (the tables are built either way): 0 =
+ * every lane takes the flat tables, 1 = windows of at most JUMP_LINE_W bases
+ * take their line (default), with all the loads of that round trip issued
+ * per 16-lane group where the tables are past the translation reach
+ * (split_for, as for the other gathers), 2 = the lines with the window's loads
+ * never split (the measured alternative, slower at 3 Gbase: DESIGN.md 5a''').
+ * Process-wide, read where jump_min is read. */
+extern "C" int32_t kfmi_set_jump_lines(uint32_t mode)
+{
+  if (mode > 2) return KFMI_E_BAD_ARGUMENT;
+  g_jump_lines.store((int) mode, std::memory_order_relaxed);
+  return KFMI_SUCCESS;
+}
+
+extern "C" uint32_t kfmi_jump_lines(void)
+{
+  const int v = g_jump_lines.load(std::memory_order_relaxed);
+  if (v >= 0) return (uint32_t) v;
+  static const uint32_t env = [] {   /* KFMI_JUMP_LINES, read once per process */
+    const char* e = getenv("KFMI_JUMP_LINES");
+    if (!e || !*e) return 1u;
+    const int x = atoi(e);
+    return x < 0 || x > 2 ? 1u : (uint32_t) x;
+  }();
+  return env;
+}
+
+static uint64_t text_words(uint64_t n) { return jump_text_words(n); }
+
+/* The host's view of jump_line_at (kfmi_device.h), for the tests: out[0 .. 5] =
+ * the lines' first dword in the allocation, the line count, and the ISA dword,
+ * first window dword (both from the lines' start), bit shift and dword count
+ * of a jump with nb bases left at text position p of an n-base text. */
+extern "C" int32_t kfmi_jump_line_geometry(uint64_t n, uint64_t p, uint32_t nb, uint64_t* out)
+{
+  if (!out || n < 1 || n >= 0xFFFFFFFFull || p > n || nb < 1 || nb > JUMP_LINE_W || nb > p) return KFMI_E_BAD_ARGUMENT;
+  const JumpLineAt at = jump_line_at((uint32_t) n, (uint32_t) p, nb);
+  out[0] = jump_lines_off(n + 1);
+  out[1] = jump_line_count(n);
+  out[2] = at.isa_dw;
+  out[3] = at.text_dw;
+  out[4] = at.shift;
+  out[5] = at.ndw;
+  return KFMI_SUCCESS;
+}
 
 /* The auto rule (kstep_fmi.h): host arithmetic only. */
 extern "C" uint32_t kfmi_jump_auto(uint64_t rows, uint32_t K, uint64_t budget_bytes)
@@ -198,27 +245,30 @@ void free_jump(kfmi_dev_index* di)
 }
 
 /* The tables of a device copy built into di->jump_sa (caller holds ftab_mu):
- * one allocation [sa | isa | text] that stays, so the kernel carries one
- * pointer, and one of 8 B x rows that goes.  The pointers ping-pong between
- * the sa and isa parts, the distances between the halves of the other; the
- * round count is known, so the walk starts in the part that leaves the last
- * pointers in `sa`.  KFMI_E_DEVICE_ALLOC when the two do not fit;
+ * one allocation [sa | isa | text | lines] that stays, so the kernel carries
+ * one pointer.  The pointers ping-pong between the sa and isa parts, the
+ * distances between two halves of the lines' part (32 dwords for every 16
+ * rows and two lines more: at least 2 x rows dwords); the round count is
+ * known, so the walk starts in the part that leaves the last pointers in
+ * `sa`.  KFMI_E_DEVICE_ALLOC when it does not fit;
  * KFMI_SUCCESS with no tables (di->jump_none = 1) when the index fails the
  * exactness check. */
 static int32_t build_jump(kfmi_dev_index* di, hipStream_t st)
 {
   const uint64_t rows = di->bwtsize, n = rows - 1, words = text_words(n);
-  uint32_t *keep = nullptr, *tmp = nullptr, *bad = nullptr;
+  const uint64_t loff = jump_lines_off(rows), lines = jump_line_count(n);
+  uint32_t *keep = nullptr, *bad = nullptr;
   auto done = [&](int32_t code) {
     if (keep) (void) hipFree(keep);
-    if (tmp) (void) hipFree(tmp);
     if (bad) (void) hipFree(bad);
     (void) hipGetLastError();
     return code;
   };
-  if (hipMalloc((void**) &keep, 4 * (2 * rows + words)) != hipSuccess || hipMalloc((void**) &tmp, 8 * rows) != hipSuccess ||
-      hipMalloc((void**) &bad, 8) != hipSuccess)
+  /* the lines hold the 2 x rows distances: DW * (n / S + 2) >= (DW / S) * (n + 1) */
+  static_assert(JUMP_LINE_DW >= 2 * JUMP_LINE_S, "two distance dwords per row fit the lines' part");
+  if (hipMalloc((void**) &keep, 4 * (loff + lines * JUMP_LINE_DW)) != hipSuccess || hipMalloc((void**) &bad, 8) != hipSuccess)
     return done(KFMI_E_DEVICE_ALLOC);
+  uint32_t* tmp = keep + loff;
   uint32_t* a[4] = {keep, tmp, keep + rows, tmp + rows};   /* next, dist and their twins */
   const uint32_t split = split_for(8 * rows, LAY_INTER) == 4u ? 1u : 0u;
   const dim3 grid(grid_blocks((rows + 255) / 256, 1u << 20));
@@ -257,7 +307,9 @@ static int32_t build_jump(kfmi_dev_index* di, hipStream_t st)
   l.jump_words = words;
   l.jump_split = l.ix.split == 1u ? 0u : 1u;
   l.num = n;
-  if (dispatch(Op::JumpText, di->K, di->nb, di->layout, l) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+  l.jump_lines = tmp;   /* the distances are spent */
+  if (dispatch(Op::JumpText, di->K, di->nb, di->layout, l) != hipSuccess ||
+      dispatch(Op::JumpLines, di->K, di->nb, di->layout, l) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
     return done(KFMI_E_KERNEL);
   di->jump_sa = keep;   /* published complete; never replaced */
   keep = nullptr;
@@ -305,7 +357,9 @@ int32_t use_jump(kfmi_dev_index* di, hipStream_t st, IdxArgs& ix, uint32_t want)
   }
   ix.jsa = di->jump_sa;
   ix.jump_min = g_jump_min.load(std::memory_order_relaxed);
-  ix.jump_split = split_for(8ull * di->bwtsize, LAY_INTER);
+  const uint32_t lines = kfmi_jump_lines();
+  const bool split4 = split_for(8ull * di->bwtsize, LAY_INTER) == 4u;
+  ix.jump_split = (split4 ? JUMP_SPLIT4 : 0u) | (lines ? JUMP_LINES : 0u) | (lines == 1u && split4 ? JUMP_LINES_GROUPED : 0u);
   return KFMI_SUCCESS;
 }
 
@@ -315,7 +369,13 @@ static uint64_t jump_bytes_of(kfmi_dev_index* di)
   return di->jump_sa ? 8ull * di->bwtsize + 4 * text_words(di->bwtsize - 1) : 0ull;
 }
 
-extern "C" uint64_t kfmi_device_jump_bytes(void* index)
+static uint64_t jump_line_bytes_of(kfmi_dev_index* di)
+{
+  std::lock_guard<std::mutex> lk(di->ftab_mu);
+  return di->jump_sa ? 4ull * JUMP_LINE_DW * jump_line_count(di->bwtsize - 1) : 0ull;
+}
+
+static uint64_t sum_members(void* index, uint64_t (*of)(kfmi_dev_index*))
 {
   kfmi_fmi_t* f = (kfmi_fmi_t*) index;
   if (!f) return 0;
@@ -323,12 +383,17 @@ extern "C" uint64_t kfmi_device_jump_bytes(void* index)
   uint64_t b = 0;
   if (f->grp) {
     const GroupIndex* g = (const GroupIndex*) f->grp;
-    for (int i = 0; i < g->n; ++i) b += jump_bytes_of(g->di[i]);
+    for (int i = 0; i < g->n; ++i) b += of(g->di[i]);
   } else if (f->dev) {
-    b = jump_bytes_of(f->dev);
+    b = of(f->dev);
   }
   return b;
 }
+
+extern "C" uint64_t kfmi_device_jump_bytes(void* index) { return sum_members(index, jump_bytes_of); }
+
+/* the line table's bytes, which kfmi_device_jump_bytes does not count */
+extern "C" uint64_t kfmi_device_jump_line_bytes(void* index) { return sum_members(index, jump_line_bytes_of); }
 
 /* Test accessor: the tables of the single-device copy, or of member `member`
  * of a device group, copied to sa[rows], isa[rows] and text[text_words];
@@ -357,6 +422,31 @@ extern "C" int32_t kfmi_device_jump_tables(void* index, uint32_t member, uint32_
   HIP_OK(hipMemcpy(sa, di->jump_sa, 4ull * rows, hipMemcpyDeviceToHost));
   HIP_OK(hipMemcpy(isa, di->jump_sa + rows, 4ull * rows, hipMemcpyDeviceToHost));
   HIP_OK(hipMemcpy(text, di->jump_sa + 2 * rows, 4ull * words, hipMemcpyDeviceToHost));
+  return KFMI_SUCCESS;
+}
+
+/* Test accessor: the raw line table of the same copy, `lines` lines of 32
+ * dwords, the padding line included; the same codes. */
+extern "C" int32_t kfmi_device_jump_lines(void* index, uint32_t member, uint32_t* out, uint64_t lines)
+{
+  kfmi_fmi_t* f = (kfmi_fmi_t*) index;
+  if (!f || !out) return KFMI_E_BAD_ARGUMENT;
+  DeviceGuard dg;
+  std::shared_lock<RwLock> lk(index_lock(f));
+  kfmi_dev_index* di = f->dev;
+  if (f->grp) {
+    const GroupIndex* g = (const GroupIndex*) f->grp;
+    if ((int) member >= g->n) return KFMI_E_BAD_ARGUMENT;
+    di = g->di[member];
+  } else if (member) {
+    return KFMI_E_BAD_ARGUMENT;
+  }
+  if (!di) return KFMI_E_NOT_ON_DEVICE;
+  std::lock_guard<std::mutex> tl(di->ftab_mu);
+  if (!di->jump_sa) return KFMI_E_NOT_ON_DEVICE;
+  if (lines != jump_line_count(di->bwtsize - 1)) return KFMI_E_BAD_ARGUMENT;
+  if (hipSetDevice(di->device) != hipSuccess) return KFMI_E_NO_DEVICE;
+  HIP_OK(hipMemcpy(out, di->jump_sa + jump_lines_off(di->bwtsize), 4ull * JUMP_LINE_DW * lines, hipMemcpyDeviceToHost));
   return KFMI_SUCCESS;
 }
 

@@ -225,7 +225,10 @@ __device__ __forceinline__ void fetch_ends_split(const IdxArgs& ix, const uint32
  * round trip, taken only when a lane of the wave jumps, loads the text window
  * (dwords of jtext, issued together, each lane only its own words) and
  * jisa[p - tK] -- its address clamped to 0 before the load when p < tK.  A
- * lane whose compare fails keeps the state it had, never jumps again and goes
+ * window of at most JUMP_LINE_W bases and its ISA entry come from one 128-byte
+ * line of the line table instead (DESIGN.md 5a''', IdxArgs::jsa): a per-lane
+ * choice of addresses for the same loads, the same wait and the same compare.
+ * A lane whose compare fails keeps the state it had, never jumps again and goes
  * on through the skip lookups and K-steps, so it returns the very empty
  * interval the walk returns. */
 template <class G, int MAXW, int SPLIT, bool JUMP = false>
@@ -261,7 +264,7 @@ __device__ __forceinline__ void skip_walk(const IdxArgs& ix, const uint32_t (&cw
     uint32_t p = SKIP_NONE;
     if constexpr (JUMP) {
       jmp = row1 && !(fl & 2u) && L[0] < ix.bwtsize && (steps - pos) * (uint32_t) G::K >= ix.jump_min;
-      if (ix.jump_split == 4u) {   /* wave-uniform */
+      if (ix.jump_split & JUMP_SPLIT4) {   /* wave-uniform */
 #pragma unroll
         for (int g = 0; g < 4; ++g)
           if (jmp && grp == g) p = ix.jsa[L[0]];
@@ -309,21 +312,48 @@ __device__ __forceinline__ void skip_walk(const IdxArgs& ix, const uint32_t (&cw
         const bool ok = jmp && p < ix.bwtsize && p >= nb;             /* SKIP_NONE fails the first test */
         const uint32_t q = ok ? p - nb : 0u;                          /* in range before the load is issued */
         const uint32_t off = ok ? ix.bwtsize - 1u - p : 0u;                /* the stream at p starts at bit 2 * off */
-        const uint32_t tw = off >> 4, tsh = (off & 15u) * 2u;
+        uint32_t tsh = (off & 15u) * 2u;
         const uint32_t nw = ok ? (nb + 15u) >> 4 : 0u;                /* words compared, <= MAXW */
+        /* per lane: where its window and its ISA entry lie, and how many words
+         * of the window go out.  The flat tables take nw + 1 words of jtext and
+         * jisa[q]; a lane with nb <= JUMP_LINE_W takes both from its one line
+         * (DESIGN.md 5a'''), and there only the words the compare needs, so no
+         * load leaves the line.  One set of loads for both kinds of lane. */
+        const uint32_t* tp = ix.jsa + (2ull * ix.bwtsize + (off >> 4));
+        const uint32_t* ip = ix.jsa + ((uint64_t) ix.bwtsize + q);
+        uint32_t lim = ok ? nw + 1u : 0u;
+        if (ok && (ix.jump_split & JUMP_LINES) && nb <= JUMP_LINE_W) {
+          const JumpLineAt at = jump_line_at(ix.bwtsize - 1u, p, nb);
+          const uint32_t* lb = ix.jsa + jump_lines_off(ix.bwtsize);
+          tp = lb + at.text_dw;
+          ip = lb + at.isa_dw;
+          tsh = at.shift;
+          lim = at.ndw;
+        }
         uint32_t tx[MAXW + 1];
 #pragma unroll
-        for (int j = 0; j <= MAXW; ++j) {
-          tx[j] = 0u;
-          if (ok && (uint32_t) j <= nw) tx[j] = ix.jsa[2ull * ix.bwtsize + tw + (uint32_t) j];
-        }
+        for (int j = 0; j <= MAXW; ++j) tx[j] = 0u;
         uint32_t r = SKIP_NONE;
-        if (ix.jump_split == 4u) {   /* wave-uniform */
+        if (ix.jump_split & JUMP_LINES_GROUPED) {   /* wave-uniform: all of a lane's loads under its group's mask */
 #pragma unroll
           for (int g = 0; g < 4; ++g)
-            if (ok && grp == g) r = ix.jsa[(uint64_t) ix.bwtsize + q];
-        } else if (ok) {
-          r = ix.jsa[(uint64_t) ix.bwtsize + q];
+            if (ok && grp == g) {
+#pragma unroll
+              for (int j = 0; j <= MAXW; ++j)
+                if ((uint32_t) j < lim) tx[j] = tp[j];
+              r = *ip;
+            }
+        } else {
+#pragma unroll
+          for (int j = 0; j <= MAXW; ++j)
+            if ((uint32_t) j < lim) tx[j] = tp[j];
+          if (ix.jump_split & JUMP_SPLIT4) {   /* wave-uniform */
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+              if (ok && grp == g) r = *ip;
+          } else if (ok) {
+            r = *ip;
+          }
         }
         uint32_t diff = 0u;
 #pragma unroll
@@ -865,6 +895,32 @@ __global__ __launch_bounds__(256) void jump_text_kernel(IdxArgs ix, const uint32
   }
 }
 
+/* Text jump, the line table (DESIGN.md 5a''', IdxArgs::jsa): one thread per
+ * output dword, streaming.  Dword t of line j is, for t < S, isa[n - e] at
+ * e = S * j + t (SKIP_NONE where e > n), and for t >= S the stream slots
+ * [16 * (j + t - 31), + 16): the line's text half starts on a word boundary
+ * of jtext, so a text dword is a copy of one of its words, zero outside them. */
+template <class G>
+__global__ __launch_bounds__(256) void jump_lines_kernel(const uint32_t* __restrict__ isa, const uint32_t* __restrict__ text,
+                                                         uint64_t n, uint64_t words, uint64_t lines,
+                                                         uint32_t* __restrict__ out)
+{
+  const uint64_t total = lines * JUMP_LINE_DW;
+  for (uint64_t i = (uint64_t) blockIdx.x * 256 + threadIdx.x; i < total; i += (uint64_t) gridDim.x * 256) {
+    const uint64_t j = i / JUMP_LINE_DW;
+    const uint32_t t = (uint32_t) (i % JUMP_LINE_DW);
+    uint32_t v;
+    if (t < JUMP_LINE_TEXT) {
+      const uint64_t e = j * JUMP_LINE_S + t;
+      v = e <= n ? isa[n - e] : SKIP_NONE;
+    } else {
+      const uint64_t w = j + t;   /* word w - (DW - 1) of the stream */
+      v = w >= JUMP_LINE_DW - 1 && w - (JUMP_LINE_DW - 1) < words ? text[w - (JUMP_LINE_DW - 1)] : 0u;
+    }
+    out[i] = v;
+  }
+}
+
 /* Remainder table for reads with m % K = rem (1 <= rem < K): [L, R) of every
  * rem-base string x (base m-1 at bits 0-1, the code order of the K-steps).
  * A K-step from [0, n+1) gives the suffix-array range of a K-mer, so
@@ -1122,6 +1178,9 @@ struct SearchLaunch {
   uint32_t* jump_text;
   uint64_t jump_words;
   uint32_t jump_split;
+  /* text jump, the line table (Op::JumpLines): jump_isa and jump_words words of jump_text of a num-base text ->
+     jump_line_count(num) lines at jump_lines */
+  uint32_t* jump_lines;
 };
 
 template <class G, int SPLIT>
@@ -1148,12 +1207,15 @@ static void launch_task_split(const SearchLaunch& a)
         const size_t lds_skip = std::max(lds, (size_t) 4 * 64 * 4 * (size_t) a.maxw);
         if constexpr (G::LAY == LAY_INTER || G::LAY == LAY_MID) {
           if (a.ix.jsa) {   /* with the text jump (DESIGN.md 5a'') */
+            IdxArgs ix = a.ix;
+            if ((ix.jump_split & JUMP_LINES_GROUPED) && a.m > JUMP_LINES_GROUPED_MAX_M)
+              ix.jump_split &= ~(JUMP_LINES | JUMP_LINES_GROUPED);   /* long reads: the flat tables' form is faster */
             if (a.maxw == 8)
               hipLaunchKernelGGL((task_kernel<G, 1, 8, SPLIT, true, true>), dim3((uint32_t) blocks), dim3(256), lds_skip,
-                                 a.st, a.ix, a.qp, a.ascii, a.m, a.num, a.steps, a.nwords, a.res);
+                                 a.st, ix, a.qp, a.ascii, a.m, a.num, a.steps, a.nwords, a.res);
             else
               hipLaunchKernelGGL((task_kernel<G, 1, 16, SPLIT, true, true>), dim3((uint32_t) blocks), dim3(256), lds_skip,
-                                 a.st, a.ix, a.qp, a.ascii, a.m, a.num, a.steps, a.nwords, a.res);
+                                 a.st, ix, a.qp, a.ascii, a.m, a.num, a.steps, a.nwords, a.res);
             return;
           }
         }
@@ -1394,7 +1456,19 @@ static hipError_t launch_jump_text(const SearchLaunch& a)
   return hipErrorInvalidValue;
 }
 
-enum class Op { Task, Coop, Count, Locate, Ftab, RemTab, CountLines, Derive, PermCheck, Skip0, JumpText };
+template <class G>
+static hipError_t launch_jump_lines(const SearchLaunch& a)
+{
+  if constexpr (G::K <= 2 && (G::LAY == LAY_INTER || G::LAY == LAY_MID)) {
+    const uint64_t lines = jump_line_count(a.num);
+    hipLaunchKernelGGL((jump_lines_kernel<G>), dim3(grid_blocks((lines * JUMP_LINE_DW + 255) / 256, 1u << 20)), dim3(256), 0,
+                       a.st, a.jump_isa, a.jump_text, a.num, a.jump_words, lines, a.jump_lines);
+    return hipGetLastError();
+  }
+  return hipErrorInvalidValue;
+}
+
+enum class Op { Task, Coop, Count, Locate, Ftab, RemTab, CountLines, Derive, PermCheck, Skip0, JumpText, JumpLines };
 
 /* Defined here, instantiated once per (K, NB, LAY) in kfmi_inst_*.hip. */
 template <int K, int NB, int LAY>
@@ -1412,6 +1486,7 @@ hipError_t dispatch_one(Op op, const SearchLaunch& a, unsigned long long* d_tota
     case Op::PermCheck: return launch_perm<G>(a);
     case Op::Skip0: return launch_skip0<G>(a);
     case Op::JumpText: return launch_jump_text<G>(a);
+    case Op::JumpLines: return launch_jump_lines<G>(a);
     default: return launch_count<G>(a, d_total);
   }
 }

@@ -133,6 +133,11 @@ def load() -> ctypes.CDLL:
         "kfmi_jump_auto": (u32, [u64, u32, u64]),
         "kfmi_device_jump_bytes": (u64, [vp]),
         "kfmi_device_jump_tables": (i32, [vp, u32, vp, vp, u64, vp, u64]),
+        "kfmi_set_jump_lines": (i32, [u32]),
+        "kfmi_jump_lines": (u32, []),
+        "kfmi_device_jump_line_bytes": (u64, [vp]),
+        "kfmi_device_jump_lines": (i32, [vp, u32, vp, u64]),
+        "kfmi_jump_line_geometry": (i32, [u64, u64, u32, ctypes.POINTER(ctypes.c_uint64)]),
         "kfmi_set_fused": (i32, [i32]),
         "kfmi_set_walk_check": (i32, [u32]),
         "kfmi_fail_index_uploads": (i32, [u32]),
@@ -249,6 +254,27 @@ def set_jump_min(bases: int) -> None:
 
 def jump_min() -> int:
     return int(load().kfmi_jump_min())
+
+
+def set_jump_lines(mode: int) -> None:
+    """The text jump's line table: 0 = windows from the flat tables, 1 (the
+    default) = from the lines, 2 = from the lines with the window's loads
+    never split into 16-lane groups; process-wide (KFMI_JUMP_LINES).  Under
+    1, on tables past the translation reach, reads longer than 192 bases take
+    the flat tables' form (kstep_fmi.h).  No setting changes a result."""
+    _check(load().kfmi_set_jump_lines(int(mode)), f"set_jump_lines({mode})")
+
+
+def jump_lines() -> int:
+    return int(load().kfmi_jump_lines())
+
+
+def jump_line_geometry(n: int, p: int, nb: int):
+    """(lines' first dword, line count, ISA dword, first window dword, bit
+    shift, dwords read) of a jump with nb bases left at text position p."""
+    out = (ctypes.c_uint64 * 6)()
+    _check(load().kfmi_jump_line_geometry(int(n), int(p), int(nb), out), f"jump_line_geometry({n}, {p}, {nb})")
+    return tuple(int(x) for x in out)
 
 
 def jump_auto(rows: int, k: int, budget_bytes: int) -> bool:
@@ -482,6 +508,18 @@ class Index(_Handle):
         _check(load().kfmi_device_jump_tables(self._p, int(member), as_p(sa), as_p(isa), rows, as_p(text), words),
                "jump_tables")
         return sa, isa, text
+
+    def jump_line_bytes(self) -> int:
+        """Bytes of the text jump's line tables (all members of a group; not in jump_bytes)."""
+        return int(load().kfmi_device_jump_line_bytes(self._p))
+
+    def jump_lines(self, member: int = 0):
+        """Test accessor: the raw line table, uint32 [n // 16 + 2, 32]."""
+        lines = (int(self.header()["bwtsize"]) - 1) // 16 + 2
+        out = np.empty((lines, 32), dtype=np.uint32)
+        _check(load().kfmi_device_jump_lines(self._p, int(member), out.ctypes.data_as(ctypes.c_void_p), lines),
+               "jump_lines")
+        return out
 
     def skip_table(self):
         """Test accessor: (J, uint32 [rows, 2] of {row, code}) of the single-device copy's skip table."""

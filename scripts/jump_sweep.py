@@ -13,8 +13,10 @@ tables' bytes.  One JSON line per (round, setting).
 Lengths: per read length m, `queries` reads sampled like the bench's (seed
 10); the mean HIP-event LF time of 12 searches after 12 warm-up ones under each
 of: the skip walk (set_jump(0)), the jump at any remaining length (jump_min 1),
-the jump at the default jump_min, the skip walk again; results checked equal
-to the first.  One JSON line per m.
+the jump at the default jump_min, the same from the flat tables
+(set_jump_lines(0)) and from the lines with unsplit window loads
+(set_jump_lines(2), DESIGN.md 5a'''), the skip walk again; results checked
+equal to the first.  One JSON line per m.
 """
 from __future__ import annotations
 
@@ -32,7 +34,7 @@ sys.path.insert(0, str(ROOT / "k-step_fm-index_amd"))
 import kstep_fmi as K  # noqa: E402
 from kstep_fmi import synth  # noqa: E402
 
-LENGTHS = "32,40,48,64,72,80,88,96,100,112,128,144,150,160"
+LENGTHS = "32,40,48,64,72,80,88,96,100,112,128,144,150,160,240,256"
 UPLOADS = (("no tables", 0, 0, 0), ("ftab", "auto", 0, 0), ("ftab, skip", "auto", "auto", 0),
            ("ftab, skip, jump", "auto", "auto", "auto"))
 
@@ -42,6 +44,7 @@ def defaults():
     K.set_skip("auto")
     K.set_jump("auto")
     K.set_jump_min(K.JUMP_MIN_DEFAULT)
+    K.set_jump_lines(1)
 
 
 def upload_rows(idx, rounds: int):
@@ -56,7 +59,8 @@ def upload_rows(idx, rounds: int):
             wall = time.perf_counter() - t0
             print(json.dumps({"round": rnd, "what": what, "upload_s": round(wall, 4),
                               "index_bytes": idx.device_bytes(), "ftab_bytes": idx.ftab_bytes(),
-                              "skip_bytes": idx.skip_bytes(), "jump_bytes": idx.jump_bytes()}), flush=True)
+                              "skip_bytes": idx.skip_bytes(), "jump_bytes": idx.jump_bytes(),
+                              "jump_line_bytes": idx.jump_line_bytes()}), flush=True)
     defaults()
     idx.free_gpu()
     K.transfer_to_gpu(idx, None, None)
@@ -69,11 +73,13 @@ def length_row(idx, text, m: int, nq: int) -> dict:
     K.transfer_to_gpu(idx, q, r)
     row = {"m": m, "queries": nq, "jump_min_default": K.JUMP_MIN_DEFAULT}
     first = None
-    settings = (("skip", 0, K.JUMP_MIN_DEFAULT), ("jump_any", "auto", 1),
-                ("jump_default", "auto", K.JUMP_MIN_DEFAULT), ("skip_again", 0, K.JUMP_MIN_DEFAULT))
-    for name, jump, jmin in settings:
+    settings = (("skip", 0, K.JUMP_MIN_DEFAULT, 1), ("jump_any", "auto", 1, 1),
+                ("jump_default", "auto", K.JUMP_MIN_DEFAULT, 1), ("jump_lines0", "auto", K.JUMP_MIN_DEFAULT, 0),
+                ("jump_lines_unsplit", "auto", K.JUMP_MIN_DEFAULT, 2), ("skip_again", 0, K.JUMP_MIN_DEFAULT, 1))
+    for name, jump, jmin, lines in settings:
         K.set_jump(jump)
         K.set_jump_min(jmin)
+        K.set_jump_lines(lines)
         lf = []
         for _ in range(24):
             K.search(idx, q, r)
