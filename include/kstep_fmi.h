@@ -664,6 +664,52 @@ int32_t kfmi_search_seeds(void *index, void *queries, void *intervals, void *spa
 int32_t kfmi_search_seeds_cpu(void *index, void *queries, void *intervals, void *spans,
                               uint32_t max_seeds, uint32_t strands, int32_t nthreads);
 
+/* ---- walk trace (tests and diagnosis; not in the reference, not timed) -------
+ * The fused forward task kernel ends a walk early through three shortcuts --
+ * the jump start, the skip table and the text jump (DESIGN.md 5a .. 5a''') --
+ * and each of them checks itself: a lookup that does not apply leaves the lane
+ * walking, so a shortcut that never fires returns the same intervals as one
+ * that always does.  kfmi_search_trace runs the search kfmi_search would run on
+ * the same resident handles under the calling thread's settings -- the same
+ * tables, the same fetch form, the same launch rules, through the same host
+ * code -- with the traced instantiation of the same kernel body, writes the
+ * intervals into `results` as kfmi_search does, and copies one record of four
+ * words per read to the host array `trace` (4 * num words, read q at 4 * q):
+ *   word 0  what the walk took: bits 0-15 the ordinary K-steps, bits 16-23 the
+ *           skip lookups that matched (each covers 16 / K steps), bits 24-31
+ *           those that did not (a lane stops looking up after its first);
+ *   word 1  the text jump, 0 when the lane never tried one (it tries at most
+ *           once): bit 0 tried; bit 1 the window and the ISA entry came from a
+ *           line of the line table (else from the flat tables; only set when
+ *           the loads were issued, i.e. not on KFMI_TRACE_JUMP_REFUSED); bits
+ *           2-3 the outcome, KFMI_TRACE_JUMP_*: TAKEN, REFUSED before the loads
+ *           (the row holds no text position, or fewer bases precede it than are
+ *           left), DIFFERED (the window is not the read's remaining bases),
+ *           BAD_ISA (the ISA entry is no row; never on a valid table); bits
+ *           4-15 the K-step position `pos` at which it tried; bits 16-31 the
+ *           bases left there, (steps - pos) * K;
+ *   word 2  the K-steps the jump start covered: 0, or the table's step count;
+ *   word 3  IdxArgs::jump_split as the kernel received it, after the launch's
+ *           read-length rule: bit 2 the gathers in four 16-lane groups, 0x100
+ *           the line table in use, 0x200 its grouped form; 1 without the jump.
+ * Steps + 16 / K * matches + word 2 is the K-step count of the read, unless the
+ * jump was TAKEN (then pos + bases left / K is).
+ *   Only what the text jump serves has a traced kernel: one device, the
+ * plain-counter task backends ("task", "task-mid"), K = 1, 2, queries whose
+ * ASCII rows are resident and fit the fused packing (at most 256 bases, fused
+ * packing on).  Everything else -- device-group handles, the coop and
+ * AltCounters backends, K = 3 / 4, packed or longer queries -- returns
+ * KFMI_E_NOT_IMPLEMENTED and a null `trace` KFMI_E_BAD_ARGUMENT, before anything
+ * runs or is written.  With every table off the traced launch still takes the
+ * walk of the tables' kernel and records plain steps only. */
+enum {
+  KFMI_TRACE_STEP = 1u, KFMI_TRACE_SKIP_HIT = 1u << 16, KFMI_TRACE_SKIP_MISS = 1u << 24,
+  KFMI_TRACE_JUMP_TRIED = 1u, KFMI_TRACE_JUMP_LINE = 2u,
+  KFMI_TRACE_JUMP_OUT_SHIFT = 2, KFMI_TRACE_JUMP_POS_SHIFT = 4, KFMI_TRACE_JUMP_NB_SHIFT = 16,
+  KFMI_TRACE_JUMP_TAKEN = 0, KFMI_TRACE_JUMP_REFUSED = 1, KFMI_TRACE_JUMP_DIFFERED = 2, KFMI_TRACE_JUMP_BAD_ISA = 3
+};
+int32_t kfmi_search_trace(void *index, void *queries, void *results, uint32_t *trace);
+
 /* Diagnostic (not in the reference): replays the line requests a
  * task-mid / coop-mid search of `queries` makes (MID128 layout, K = 2, d = 64,
  * m % K == 0, both uploaded) without the LF chain's dependence: a trace launch

@@ -12,6 +12,7 @@
 #include <stdlib.h>
 #include <algorithm>
 
+#include "../../../include/kstep_fmi.h"
 #include "kfmi_device.h"
 #include "kfmi_grid.h"
 #include "kfmi_strands.h"
@@ -197,6 +198,22 @@ __device__ __forceinline__ void fetch_ends_split(const IdxArgs& ix, const uint32
   }
 }
 
+/* The trace policy of skip_walk and task_kernel (TR, below): whether the walk
+ * records what it does, and the type of the pointer it records through -- the
+ * records of a launch (Trace) or an empty object (NoTrace, every search). */
+struct NoTrace {
+  static constexpr bool ON = false;
+  struct Out {};
+  static Out from(uint4*) { return Out{}; }
+  __device__ static Out at(Out, uint64_t) { return Out{}; }
+};
+struct Trace {
+  static constexpr bool ON = true;
+  typedef uint4* Out;
+  static Out from(uint4* t) { return t; }
+  __device__ static Out at(Out t, uint64_t q) { return t + q; }   /* read q's record */
+};
+
 /* The walk of the fused task kernel with the skip table (IdxArgs::skip,
  * DESIGN.md 5a'): every lane keeps its own step position `pos`, and each
  * round of the wave-uniform loop a lane takes either one table lookup or one
@@ -230,12 +247,20 @@ __device__ __forceinline__ void fetch_ends_split(const IdxArgs& ix, const uint32
  * choice of addresses for the same loads, the same wait and the same compare.
  * A lane whose compare fails keeps the state it had, never jumps again and goes
  * on through the skip lookups and K-steps, so it returns the very empty
- * interval the walk returns. */
-template <class G, int MAXW, int SPLIT, bool JUMP = false>
+ * interval the walk returns.
+ *   TR (kstep_fmi.h kfmi_search_trace): with Trace the same
+ * body counts what the lane does -- K-steps, skip lookups that matched and that
+ * did not, its one text jump -- and stores one 16-byte record when it leaves
+ * the loop.  Every hook is an `if constexpr (TR::ON)` block; with NoTrace, the
+ * default, none of them is instantiated and `tr` is an empty object. */
+template <class G, int MAXW, int SPLIT, bool JUMP = false, class TR = NoTrace>
 __device__ __forceinline__ void skip_walk(const IdxArgs& ix, const uint32_t (&cw)[MAXW], uint32_t steps, uint32_t pos,
-                                          uint32_t& Lq, uint32_t& Rq)
+                                          uint32_t& Lq, uint32_t& Rq, typename TR::Out tr = typename TR::Out{})
 {
   static_assert(G::K <= 2 && MAXW > 0, "skip table: fused task kernels at K <= 2");
+  /* TR: the record's words 0 .. 2 (kstep_fmi.h); the start is `pos` as the caller passed it */
+  [[maybe_unused]] uint32_t tr_walk = 0, tr_jump = 0, tr_line = 0;
+  [[maybe_unused]] const uint32_t tr_start = pos;
   extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
   const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
   uint32_t* cl = reinterpret_cast<uint32_t*>(stage) + wv * (64u * MAXW) + lane;
@@ -295,15 +320,18 @@ __device__ __forceinline__ void skip_walk(const IdxArgs& ix, const uint32_t (&cw
         R[0] = lf_stream<G>(ix, R[0], c[0], sx);
       }
       ++pos;
+      if constexpr (TR::ON) tr_walk += KFMI_TRACE_STEP;
     }
     if (one) {
       if (e.x != SKIP_NONE && e.y == code) {
         L[0] = e.x;
         R[0] = e.x + 1u;
         pos += J;
+        if constexpr (TR::ON) tr_walk += KFMI_TRACE_SKIP_HIT;
       } else {
         if constexpr (JUMP) fl |= 1u;
         else dead = true;
+        if constexpr (TR::ON) tr_walk += KFMI_TRACE_SKIP_MISS;
       }
     }
     if constexpr (JUMP) {
@@ -329,6 +357,7 @@ __device__ __forceinline__ void skip_walk(const IdxArgs& ix, const uint32_t (&cw
           ip = lb + at.isa_dw;
           tsh = at.shift;
           lim = at.ndw;
+          if constexpr (TR::ON) tr_line = KFMI_TRACE_JUMP_LINE;
         }
         uint32_t tx[MAXW + 1];
 #pragma unroll
@@ -368,6 +397,15 @@ __device__ __forceinline__ void skip_walk(const IdxArgs& ix, const uint32_t (&cw
             diff |= (rw ^ tv) & (left >= 32u ? 0xFFFFFFFFu : (1u << left) - 1u);
           }
         }
+        if constexpr (TR::ON) {   /* before pos moves: where the lane stood, and how the jump ended */
+          if (jmp) {
+            const uint32_t out = !ok ? KFMI_TRACE_JUMP_REFUSED
+                                     : (diff != 0u ? KFMI_TRACE_JUMP_DIFFERED
+                                                   : (r < ix.bwtsize ? KFMI_TRACE_JUMP_TAKEN : KFMI_TRACE_JUMP_BAD_ISA));
+            tr_jump = KFMI_TRACE_JUMP_TRIED | tr_line | (out << KFMI_TRACE_JUMP_OUT_SHIFT) |
+                      (pos << KFMI_TRACE_JUMP_POS_SHIFT) | (nb << KFMI_TRACE_JUMP_NB_SHIFT);
+          }
+        }
         if (ok && diff == 0u && r < ix.bwtsize) {
           L[0] = r;
           R[0] = r + 1u;
@@ -380,6 +418,7 @@ __device__ __forceinline__ void skip_walk(const IdxArgs& ix, const uint32_t (&cw
   }
   Lq = L[0];
   Rq = R[0];
+  if constexpr (TR::ON) *tr = make_uint4(tr_walk, tr_jump, tr_start, ix.jump_split);
 }
 
 /* The walk of a seed search (kfmi_seeds.hip, kstep_fmi.h section 2, DESIGN.md
@@ -507,12 +546,16 @@ __device__ __forceinline__ void seed_walk(const IdxArgs& ix, const uint32_t (&cw
 /* SKIP (last template value, fused K <= 2 only): the walk with the skip table,
  * launched when ix.skip or ix.jsa is set; without it the kernel is the plain
  * walk.  JUMP (with SKIP, plain layouts): skip_walk with the text jump, launched
- * when ix.jsa is set; the strand and words kernels are compiled without it. */
-template <class G, int QPT, int MAXW, int SPLIT = 1, bool SKIP = false, bool JUMP = false>
+ * when ix.jsa is set; the strand and words kernels are compiled without it.
+ * TR = Trace (with SKIP): skip_walk writes read q's record to trace[q]; with
+ * NoTrace `trace` is an empty object and the kernel is what it was. */
+template <class G, int QPT, int MAXW, int SPLIT = 1, bool SKIP = false, bool JUMP = false, class TR = NoTrace>
 __global__ __launch_bounds__(256) void task_kernel(IdxArgs ix, const uint32_t* __restrict__ qp,
                                                    const uint8_t* __restrict__ ascii, uint32_t m, uint64_t num,
-                                                   uint32_t steps, uint32_t nwords, uint32_t* __restrict__ res)
+                                                   uint32_t steps, uint32_t nwords, uint32_t* __restrict__ res,
+                                                   typename TR::Out trace)
 {
+  static_assert(!TR::ON || SKIP, "walk trace: skip_walk's hooks");
   constexpr int SPW = G::SPW;
   constexpr int CW = MAXW > 0 ? (G::K == 3 ? k3_words<(MAXW > 0 ? MAXW : 1)>() : MAXW) : 1;
   static_assert(MAXW == 0 || QPT == 1, "fused packing: one query per thread");
@@ -563,7 +606,7 @@ __global__ __launch_bounds__(256) void task_kernel(IdxArgs ix, const uint32_t* _
     }
   }
   if constexpr (SKIP) {
-    skip_walk<G, MAXW, SPLIT, JUMP>(ix, cw[0], steps, skip, L[0], R[0]);
+    skip_walk<G, MAXW, SPLIT, JUMP, TR>(ix, cw[0], steps, skip, L[0], R[0], TR::at(trace, base));
     *reinterpret_cast<uint2*>(res + 2 * base) = make_uint2(L[0], R[0]);
     return;
   }
@@ -1181,14 +1224,24 @@ struct SearchLaunch {
   /* text jump, the line table (Op::JumpLines): jump_isa and jump_words words of jump_text of a num-base text ->
      jump_line_count(num) lines at jump_lines */
   uint32_t* jump_lines;
+  /* walk trace (trace_one): num records, one per read; null in every other launch */
+  uint4* trace;
 };
 
-template <class G, int SPLIT>
+/* TR = Trace (kfmi_search_trace, trace_one below): the same choices with the
+ * traced kernels, which exist for what the text jump serves -- the fused
+ * forward walk on the plain layouts at K <= 2; there a search without any table
+ * takes the tables' kernel too, so that skip_walk records its plain steps.
+ * The caller has refused everything else. */
+template <class G, int SPLIT, class TR = NoTrace>
 static void launch_task_split(const SearchLaunch& a)
 {
+  constexpr bool TRACED = G::K <= 2 && (G::LAY == LAY_INTER || G::LAY == LAY_MID);
+  static_assert(!TR::ON || TRACED, "walk trace: fused forward task kernels, plain layouts, K <= 2");
+  const typename TR::Out tr = TR::from(a.trace);
   if (a.maxw) {
     const size_t lds = 4 * (size_t) stage_slot_bytes(a.m);
-    if constexpr (G::K <= 2) {
+    if constexpr (G::K <= 2 && !TR::ON) {
       if (a.strands) {   /* strand-aware staging, then the fused kernel's own walk */
         const uint64_t tblocks = ((a.strands == 3u ? 2u : 1u) * a.num + 255) / 256;
         const size_t lds_str = std::max(lds, (size_t) 4 * 64 * 4 * (size_t) a.maxw);
@@ -1203,7 +1256,7 @@ static void launch_task_split(const SearchLaunch& a)
     }
     const uint64_t blocks = (a.num + 255) / 256;
     if constexpr (G::K <= 2) {
-      if (a.ix.skip || a.ix.jsa) {   /* the walk with the tables; LDS: the staging, then 64 x maxw code words per wave */
+      if (TR::ON || a.ix.skip || a.ix.jsa) {   /* the walk with the tables; LDS: the staging, then 64 x maxw code words per wave */
         const size_t lds_skip = std::max(lds, (size_t) 4 * 64 * 4 * (size_t) a.maxw);
         if constexpr (G::LAY == LAY_INTER || G::LAY == LAY_MID) {
           if (a.ix.jsa) {   /* with the text jump (DESIGN.md 5a'') */
@@ -1211,30 +1264,32 @@ static void launch_task_split(const SearchLaunch& a)
             if ((ix.jump_split & JUMP_LINES_GROUPED) && a.m > JUMP_LINES_GROUPED_MAX_M)
               ix.jump_split &= ~(JUMP_LINES | JUMP_LINES_GROUPED);   /* long reads: the flat tables' form is faster */
             if (a.maxw == 8)
-              hipLaunchKernelGGL((task_kernel<G, 1, 8, SPLIT, true, true>), dim3((uint32_t) blocks), dim3(256), lds_skip,
-                                 a.st, ix, a.qp, a.ascii, a.m, a.num, a.steps, a.nwords, a.res);
+              hipLaunchKernelGGL((task_kernel<G, 1, 8, SPLIT, true, true, TR>), dim3((uint32_t) blocks), dim3(256),
+                                 lds_skip, a.st, ix, a.qp, a.ascii, a.m, a.num, a.steps, a.nwords, a.res, tr);
             else
-              hipLaunchKernelGGL((task_kernel<G, 1, 16, SPLIT, true, true>), dim3((uint32_t) blocks), dim3(256), lds_skip,
-                                 a.st, ix, a.qp, a.ascii, a.m, a.num, a.steps, a.nwords, a.res);
+              hipLaunchKernelGGL((task_kernel<G, 1, 16, SPLIT, true, true, TR>), dim3((uint32_t) blocks), dim3(256),
+                                 lds_skip, a.st, ix, a.qp, a.ascii, a.m, a.num, a.steps, a.nwords, a.res, tr);
             return;
           }
         }
         if (a.maxw == 8)
-          hipLaunchKernelGGL((task_kernel<G, 1, 8, SPLIT, true>), dim3((uint32_t) blocks), dim3(256), lds_skip, a.st,
-                             a.ix, a.qp, a.ascii, a.m, a.num, a.steps, a.nwords, a.res);
+          hipLaunchKernelGGL((task_kernel<G, 1, 8, SPLIT, true, false, TR>), dim3((uint32_t) blocks), dim3(256), lds_skip,
+                             a.st, a.ix, a.qp, a.ascii, a.m, a.num, a.steps, a.nwords, a.res, tr);
         else
-          hipLaunchKernelGGL((task_kernel<G, 1, 16, SPLIT, true>), dim3((uint32_t) blocks), dim3(256), lds_skip, a.st,
-                             a.ix, a.qp, a.ascii, a.m, a.num, a.steps, a.nwords, a.res);
+          hipLaunchKernelGGL((task_kernel<G, 1, 16, SPLIT, true, false, TR>), dim3((uint32_t) blocks), dim3(256), lds_skip,
+                             a.st, a.ix, a.qp, a.ascii, a.m, a.num, a.steps, a.nwords, a.res, tr);
         return;
       }
     }
-    if (a.maxw == 8)
-      hipLaunchKernelGGL((task_kernel<G, 1, 8, SPLIT>), dim3((uint32_t) blocks), dim3(256), lds, a.st, a.ix, a.qp,
-                         a.ascii, a.m, a.num, a.steps, a.nwords, a.res);
-    else
-      hipLaunchKernelGGL((task_kernel<G, 1, 16, SPLIT>), dim3((uint32_t) blocks), dim3(256), lds, a.st, a.ix, a.qp,
-                         a.ascii, a.m, a.num, a.steps, a.nwords, a.res);
-  } else {
+    if constexpr (!TR::ON) {
+      if (a.maxw == 8)
+        hipLaunchKernelGGL((task_kernel<G, 1, 8, SPLIT>), dim3((uint32_t) blocks), dim3(256), lds, a.st, a.ix, a.qp,
+                           a.ascii, a.m, a.num, a.steps, a.nwords, a.res, tr);
+      else
+        hipLaunchKernelGGL((task_kernel<G, 1, 16, SPLIT>), dim3((uint32_t) blocks), dim3(256), lds, a.st, a.ix, a.qp,
+                           a.ascii, a.m, a.num, a.steps, a.nwords, a.res, tr);
+    }
+  } else if constexpr (!TR::ON) {
     const uint64_t blocks = (a.num + 255) / 256;
     if constexpr (G::K <= 2) {
       if (a.ix.skip && a.words_maxw) {   /* strand searches: the skip-table walk on packed words */
@@ -1249,11 +1304,11 @@ static void launch_task_split(const SearchLaunch& a)
       }
     }
     hipLaunchKernelGGL((task_kernel<G, 1, 0, SPLIT>), dim3((uint32_t) blocks), dim3(256), 0, a.st, a.ix, a.qp,
-                       a.ascii, a.m, a.num, a.steps, a.nwords, a.res);
+                       a.ascii, a.m, a.num, a.steps, a.nwords, a.res, tr);
   }
 }
 
-template <class G>
+template <class G, class TR = NoTrace>
 static hipError_t launch_task(const SearchLaunch& a)
 {
   /* the split only exists for the one-line-per-block path (d <= 128 at K=2);
@@ -1263,18 +1318,18 @@ static hipError_t launch_task(const SearchLaunch& a)
   if constexpr (G::SMALL) {
     const uint32_t want = a.ix.split;
     if constexpr (X4<G>::OK) {
-      if (want == 1) launch_task_split<G, 8>(a);
-      else launch_task_split<G, 7>(a);
+      if (want == 1) launch_task_split<G, 8, TR>(a);
+      else launch_task_split<G, 7, TR>(a);
       return hipGetLastError();
     }
     /* the words-skip kernel takes the fused skip kernel's form; the plain walk of words keeps its own */
     const int mw = a.maxw ? a.maxw : (a.ix.skip ? a.words_maxw : 0);
     if (want == 4 || (want == 2 && mw == 8)) {
-      launch_task_split<G, 4>(a);
+      launch_task_split<G, 4, TR>(a);
       return hipGetLastError();
     }
   }
-  launch_task_split<G, 1>(a);
+  launch_task_split<G, 1, TR>(a);
   return hipGetLastError();
 }
 
@@ -1468,7 +1523,8 @@ static hipError_t launch_jump_lines(const SearchLaunch& a)
   return hipErrorInvalidValue;
 }
 
-enum class Op { Task, Coop, Count, Locate, Ftab, RemTab, CountLines, Derive, PermCheck, Skip0, JumpText, JumpLines };
+/* Trace: the traced task kernels; dispatch() sends it to trace_one (below), not through dispatch_one */
+enum class Op { Task, Coop, Count, Locate, Ftab, RemTab, CountLines, Derive, PermCheck, Skip0, JumpText, JumpLines, Trace };
 
 /* Defined here, instantiated once per (K, NB, LAY) in kfmi_inst_*.hip. */
 template <int K, int NB, int LAY>
@@ -1487,6 +1543,7 @@ hipError_t dispatch_one(Op op, const SearchLaunch& a, unsigned long long* d_tota
     case Op::Skip0: return launch_skip0<G>(a);
     case Op::JumpText: return launch_jump_text<G>(a);
     case Op::JumpLines: return launch_jump_lines<G>(a);
+    case Op::Trace: return hipErrorInvalidValue;   /* trace_one */
     default: return launch_count<G>(a, d_total);
   }
 }
@@ -1507,6 +1564,20 @@ hipError_t seeds_one(const SearchLaunch& a)
 
 #define KFMI_SEEDS_INSTANTIATE(KK, NBV, LAYV) template hipError_t seeds_one<KK, NBV, LAYV>(const SearchLaunch&);
 #define KFMI_SEEDS_EXTERN(KK, NBV, LAYV) extern template hipError_t seeds_one<KK, NBV, LAYV>(const SearchLaunch&);
+
+/* The traced task kernels' launch (Op::Trace), apart from dispatch_one like the
+ * seed kernels' and for the same reason: launch_task with the traced kernels,
+ * instantiated per (K, NB, LAY) in kfmi_inst_trace_*.hip for K <= 2 on the task
+ * and task-mid layouts, called from dispatch (kfmi_search.hip). */
+template <int K, int NB, int LAY>
+hipError_t trace_one(const SearchLaunch& a)
+{
+  if (!a.trace || !a.maxw || a.strands) return hipErrorInvalidValue;
+  return launch_task<Geo<K, NB, LAY>, Trace>(a);
+}
+
+#define KFMI_TRACE_INSTANTIATE(KK, NBV, LAYV) template hipError_t trace_one<KK, NBV, LAYV>(const SearchLaunch&);
+#define KFMI_TRACE_EXTERN(KK, NBV, LAYV) extern template hipError_t trace_one<KK, NBV, LAYV>(const SearchLaunch&);
 
 }  // namespace kfmi
 

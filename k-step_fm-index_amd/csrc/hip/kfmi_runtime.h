@@ -201,8 +201,9 @@ void free_dev_queries(kfmi_dev_queries* dq);
 hipError_t h2d(void* dst, const void* src, uint64_t bytes, hipStream_t st);
 
 /* one device batch: queue pack + LF bracketed by ev[0..2], then wait (kfmi_search.hip) */
+/* trace: null, or num records on the device (kfmi_search_trace: the traced kernels, Op::Trace) */
 int32_t search_enqueue(kfmi_dev_index* di, kfmi_dev_queries* dq, uint32_t* d_res, hipStream_t st, hipEvent_t* ev,
-                       uint32_t ftab, uint32_t skip);
+                       uint32_t ftab, uint32_t skip, uint4* trace = nullptr);
 int32_t search_finish(hipStream_t st, hipEvent_t* ev, double* ms);
 
 /* strand searches (kfmi_strands.hip): dq->strand_words sized for both strands

@@ -504,9 +504,24 @@ KFMI_FOR_NB(KFMI_EXTERN, 1, LAY_MIDAC)
 KFMI_FOR_NB(KFMI_EXTERN, 2, LAY_MIDAC)
 KFMI_EXTERN(4, 2, LAY_GRP)
 KFMI_EXTERN(3, 2, LAY_GRP)
+/* trace_one<K, NB, LAY> (Op::Trace) is compiled in kfmi_inst_trace_*.hip */
+KFMI_FOR_NB(KFMI_TRACE_EXTERN, 1, LAY_INTER)
+KFMI_FOR_NB(KFMI_TRACE_EXTERN, 2, LAY_INTER)
+KFMI_FOR_NB(KFMI_TRACE_EXTERN, 1, LAY_MID)
+KFMI_FOR_NB(KFMI_TRACE_EXTERN, 2, LAY_MID)
 
 hipError_t dispatch(Op op, uint32_t K, uint32_t nb, int lay, const SearchLaunch& a, unsigned long long* d_total)
 {
+  if (op == Op::Trace) {   /* the traced task kernels: the geometries that have them */
+#define KFMI_CASE(KK, NBV, LAYV) \
+  if (K == KK && nb == NBV && lay == LAYV) return trace_one<KK, NBV, LAYV>(a);
+    KFMI_FOR_NB(KFMI_CASE, 1, LAY_INTER)
+    KFMI_FOR_NB(KFMI_CASE, 2, LAY_INTER)
+    KFMI_FOR_NB(KFMI_CASE, 1, LAY_MID)
+    KFMI_FOR_NB(KFMI_CASE, 2, LAY_MID)
+#undef KFMI_CASE
+    return hipErrorInvalidValue;
+  }
 #define KFMI_CASE(KK, NBV, LAYV)                                   \
   if (K == KK && nb == NBV && lay == LAYV) return dispatch_one<KK, NBV, LAYV>(op, a, d_total);
   KFMI_FOR_NB(KFMI_CASE, 1, LAY_INTER)
@@ -2061,7 +2076,7 @@ extern "C" int32_t transferCPUtoGPU(void* index, void* queries, void* results)
 /* Queues pack (if not fused) + LF of one device batch on `st`, bracketed by
  * ev[0..2]; search_finish waits and reads the timings. */
 int32_t search_enqueue(kfmi_dev_index* di, kfmi_dev_queries* dq, uint32_t* d_res, hipStream_t st,
-                              hipEvent_t* ev, uint32_t ftab, uint32_t skip)
+                              hipEvent_t* ev, uint32_t ftab, uint32_t skip, uint4* trace)
 {
   if (dq->device != di->device || dq->K != di->K) return KFMI_E_BAD_ARGUMENT;
   SearchLaunch a{};
@@ -2079,11 +2094,13 @@ int32_t search_enqueue(kfmi_dev_index* di, kfmi_dev_queries* dq, uint32_t* d_res
   a.steps = dq->steps;
   a.nwords = dq->nwords;
   a.res = d_res;
+  a.trace = trace;
+  if (trace && (!a.maxw || is_coop(di->backend))) return KFMI_E_NOT_IMPLEMENTED;   /* no traced kernel */
   HIP_OK(hipEventRecord(ev[0], st));
   if (!a.maxw) HIP_OK(launch_pack(dq, st));
   HIP_OK(hipEventRecord(ev[1], st));
   if (dq->num) {
-    const Op op = is_coop(di->backend) ? Op::Coop : Op::Task;
+    const Op op = trace ? Op::Trace : (is_coop(di->backend) ? Op::Coop : Op::Task);
     HIP_OK(dispatch(op, di->K, di->nb, di->layout, a));
   }
   HIP_OK(hipEventRecord(ev[2], st));
@@ -2122,6 +2139,45 @@ extern "C" int32_t kfmi_search(void* index, void* queries, void* results)
   if (!err && (!ev || !st)) err = KFMI_E_NO_DEVICE;
   if (!err) err = search_enqueue(di, q->dev, r->d_results, st, ev, ftab_bases(), tables_wanted());
   if (!err) err = search_finish(st, ev, t_ms);
+  return err;
+}
+
+/* kstep_fmi.h: kfmi_search on resident single-device handles with the traced
+ * kernels -- search_enqueue itself, so the tables, the fetch form and the
+ * launch rules are the search's own -- and one record per read copied out.
+ * Everything that has no traced kernel is refused before anything is queued. */
+extern "C" int32_t kfmi_search_trace(void* index, void* queries, void* results, uint32_t* trace)
+{
+  kfmi_fmi_t* f = (kfmi_fmi_t*) index;
+  kfmi_qrys_t* q = (kfmi_qrys_t*) queries;
+  kfmi_res_t* r = (kfmi_res_t*) results;
+  if (!f || !q || !r || !trace) return KFMI_E_BAD_ARGUMENT;
+  if (q->num != r->num) return KFMI_E_BAD_ARGUMENT;
+  DeviceGuard dg;
+  std::shared_lock<RwLock> lk(index_lock(f));
+  if (f->grp || q->grp || r->grp) return KFMI_E_NOT_IMPLEMENTED;
+  if (!f->dev || !q->dev || !r->d_results) return KFMI_E_NOT_ON_DEVICE;
+  kfmi_dev_index* di = f->dev;
+  kfmi_dev_queries* dq = q->dev;
+  if (r->d_device != di->device) return KFMI_E_BAD_ARGUMENT;
+  if (is_coop(di->backend) || (di->layout != LAY_INTER && di->layout != LAY_MID) || di->K < 1 || di->K > 2)
+    return KFMI_E_NOT_IMPLEMENTED;
+  if (!dq->ascii || !fused_maxw(di->backend, dq->K * dq->steps)) return KFMI_E_NOT_IMPLEMENTED;
+  DevCtx* ctx = nullptr;
+  int32_t err = ctx_for(di->device, &ctx);
+  hipEvent_t* ev = err ? nullptr : thread_events(di->device);
+  hipStream_t st = err ? nullptr : thread_stream(di->device);
+  if (!err && (!ev || !st)) err = KFMI_E_NO_DEVICE;
+  if (err) return err;
+  uint4* d_trace = nullptr;
+  if (hipMalloc((void**) &d_trace, 16ull * (q->num ? q->num : 1)) != hipSuccess) {
+    (void) hipGetLastError();
+    return KFMI_E_DEVICE_ALLOC;
+  }
+  err = search_enqueue(di, dq, r->d_results, st, ev, ftab_bases(), tables_wanted(), d_trace);
+  if (!err) err = search_finish(st, ev, t_ms);
+  if (!err && q->num && hipMemcpy(trace, d_trace, 16ull * q->num, hipMemcpyDeviceToHost) != hipSuccess) err = KFMI_E_KERNEL;
+  (void) hipFree(d_trace);
   return err;
 }
 

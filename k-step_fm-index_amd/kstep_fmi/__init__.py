@@ -159,6 +159,7 @@ def load() -> ctypes.CDLL:
         "kfmi_reverse_stream_host": (i32, [vp, u64, u32, u32, vp]),
         "kfmi_search_seeds": (i32, [vp, vp, vp, vp, u32, u32]),
         "kfmi_search_seeds_cpu": (i32, [vp, vp, vp, vp, u32, u32, i32]),
+        "kfmi_search_trace": (i32, [vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -851,6 +852,54 @@ def search_array(index: Index, queries: np.ndarray, backend: str | None = None,
             search_strands(index, q, r, strands)
         transfer_to_cpu(r)
         return r.array().copy()
+    finally:
+        q.close()
+        r.close()
+
+
+TRACE_JUMP_OUTCOMES = ("taken", "refused", "differed", "bad_isa")
+TRACE_FIELDS = ("steps", "skip_hits", "skip_misses", "jump_tried", "jump_pos", "jump_nb", "jump_line",
+                "jump_outcome", "start_steps", "jump_split")
+
+
+def decode_trace(records: np.ndarray) -> dict:
+    """The named fields of kfmi_search_trace's records (uint32 [N, 4],
+    kstep_fmi.h): int64 arrays of N per name in TRACE_FIELDS.  jump_outcome
+    indexes TRACE_JUMP_OUTCOMES and is -1, like jump_pos / jump_nb / jump_line,
+    for a read that never tried the jump."""
+    r = np.asarray(records, dtype=np.uint32).reshape(-1, 4).astype(np.int64)
+    tried = r[:, 1] & 1
+    no = tried == 0
+    return {
+        "steps": r[:, 0] & 0xFFFF,
+        "skip_hits": (r[:, 0] >> 16) & 0xFF,
+        "skip_misses": (r[:, 0] >> 24) & 0xFF,
+        "jump_tried": tried,
+        "jump_pos": np.where(no, -1, (r[:, 1] >> 4) & 0xFFF),
+        "jump_nb": np.where(no, -1, (r[:, 1] >> 16) & 0xFFFF),
+        "jump_line": np.where(no, -1, (r[:, 1] >> 1) & 1),
+        "jump_outcome": np.where(no, -1, (r[:, 1] >> 2) & 3),
+        "start_steps": r[:, 2],
+        "jump_split": r[:, 3],
+    }
+
+
+def search_trace(index: Index, reads: np.ndarray, backend: str | None = None):
+    """kfmi_search_trace, one shot: the search search_array runs on uint8
+    [N, m] reads under the calling thread's settings, with the traced kernels.
+    Returns (intervals uint32 [2N], records uint32 [N, 4]); decode_trace names
+    the records' fields.  For tests and diagnosis; not timed."""
+    if backend:
+        set_backend(backend)
+    q = Queries.from_array(reads)
+    r = Results.alloc(reads.shape[0])
+    rec = np.zeros((reads.shape[0], 4), dtype=np.uint32)
+    try:
+        transfer_to_gpu(index, q, r)
+        _check(load().kfmi_search_trace(index.ptr, q.ptr, r.ptr, rec.ctypes.data_as(ctypes.c_void_p)),
+               "kfmi_search_trace")
+        transfer_to_cpu(r)
+        return r.array().copy(), rec
     finally:
         q.close()
         r.close()

@@ -9,7 +9,11 @@ form of the loads (set_jump_lines(1 | 2) under set_split_class(0 | 4)).
 
 No result shows which form a lane took, so the host asserts from brute force
 what decides it: every exact read reaches one row with at least jump_min bases
-left, and how many are left there (`left_at_jump`).
+left, and how many are left there (`left_at_jump`).  What the kernel did with
+them is held by tests/test_walk_trace.py, from the kernel's own records; the
+windows test below also asks the trace that each exact read jumped with
+exactly `left_at_jump` bases left, from a line up to W bases and from the flat
+tables beyond.
 """
 import numpy as np
 import pytest
@@ -200,6 +204,11 @@ def test_windows_around_W_in_one_wave(gpu, oracle_mod, world, backend, k, d, ski
             want = _oracle(oracle_mod, world, k, d, q)
             _settings(gpu, False, skip)
             _all_forms(gpu, idx, q, backend, want, (m, skip))
+            got, rec = gpu.search_trace(idx, base, backend)      # lines 1, class 0: what the kernel did
+            _same(got, want[:2 * 64], (m, skip, "trace"))
+            did = gpu.decode_trace(rec)
+            assert (did["jump_outcome"] == 0).all() and np.array_equal(did["jump_nb"], left), (m, skip)
+            assert np.array_equal(did["jump_line"], (left <= W).astype(np.int64)), (m, skip)
         assert set(range(W - 2, W + 3, k)) <= seen, sorted(seen)
     finally:
         _defaults(gpu)

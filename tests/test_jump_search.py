@@ -201,7 +201,8 @@ def test_substitutions_ends_repeat_and_threshold(gpu, oracle_mod, world, backend
     either side.  With the skip table and, under set_jump(1), without it.
     The jump_min cases check results only: a jump returns what the walk returns,
     so they hold that both sides of the threshold are exact, not on which side
-    of it a lane jumps -- nothing observable pins the kernel's `>= jump_min`."""
+    of it a lane jumps -- the kernel's `>= jump_min` itself is held by
+    tests/test_walk_trace.py, from the kernel's own records."""
     idx = world(k, d)
     rng = np.random.default_rng(77 + k)
     try:
