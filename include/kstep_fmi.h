@@ -664,6 +664,70 @@ int32_t kfmi_search_seeds(void *index, void *queries, void *intervals, void *spa
 int32_t kfmi_search_seeds_cpu(void *index, void *queries, void *intervals, void *spans,
                               uint32_t max_seeds, uint32_t strands, int32_t nthreads);
 
+/* ---- verify seeds (not in the reference, which stops at intervals) -----------
+ * The step a mapper takes after seeding: score the read at the text position
+ * each seed implies and keep the best placement.  Tasks, their order and the
+ * S = max_seeds slots per task are those of kfmi_search_seeds (ns = 2 for
+ * BOTH, task 2q + strand; a REV task is the read P').  `intervals` and `spans`
+ * are two results handles of S * ns * num entries as the seed search leaves
+ * them on the device -- any caller-filled handles of that size are accepted
+ * too -- and `hits` is a third handle of exactly ns * num entries, entry t the
+ * record of task t.  With n the text's length, rows = n + 1, m the read length
+ * and sa the text's suffix array (sa[0] = n, the '$' suffix):
+ *   Candidates.  Slot s of task t with {L, R} and {start, len} gives the rows
+ * L, L + 1, .. in row order, below min(R, rows, L + max_occ).  A slot
+ * contributes nothing when R <= L, L >= rows, len == 0 or start + len > m.  Row
+ * r gives p = sa[r] and the origin o = p - start.  The candidate is scored iff
+ * sa[r] < rows, p >= start and o + m <= n; otherwise it is skipped and not
+ * counted.
+ *   Score: the number of j in [0, m) with base2index(P[j]) != code(T[o + j])
+ * (N -> G, lowercase like uppercase, as everywhere).
+ *   Record.  Over all scored candidates of the task, the minimum of (mism, o)
+ * in lexicographic order; KFMI_HIT_MULTI iff two distinct origins attain the
+ * minimal mism (two slots that point at one origin are one origin).  If that
+ * mism <= max_mism: x = o, y = mism | MULTI | scored << 20, scored the number
+ * of scored candidates (at most 8 * 256).  Otherwise, and with no scored
+ * candidate: x = KFMI_HIT_NONE, y = scored << 20.  The result depends on no
+ * evaluation order, and every entry of `hits` is written whatever it held.
+ *   Arguments: max_seeds 1 .. 8; strands FWD, REV or BOTH; max_occ 1 ..
+ * KFMI_VERIFY_MAX_OCC (there is no "all": a poly-A interval must not make one
+ * lane loop millions of times); max_mism any value (>= m accepts everything);
+ * exact handle sizes; reads of at most 256 bases -- else KFMI_E_BAD_ARGUMENT.
+ *   kfmi_verify_seeds covers the device copies the seed search covers ("task",
+ * "task-mid", K = 1, 2, one device) and needs the queries' ASCII rows on the
+ * device.  KFMI_E_NOT_IMPLEMENTED: the coop and AltCounters backends, K = 3 / 4,
+ * device-group handles, KFMI_UPLOAD=packed queries, and a device copy whose
+ * index fails the text jump's exactness check.  A refused call writes nothing.
+ *   Tables: the call reads the flat tables [sa | isa | text] of the text jump
+ * and never the FM index.  Where the device copy has none it builds them, on
+ * the path kfmi_set_jump(1) takes at a first search and whatever the calling
+ * thread's jump setting is; KFMI_E_DEVICE_ALLOC when they do not fit.  Tables
+ * built this way stay with the device copy like any others: later searches
+ * under the auto setting may use them, with the same results.
+ *   kfmi_last_timing: total, 0, the verify kernel (ms).
+ *   kfmi_verify_seeds_cpu: the same definition on the host (OpenMP, nthreads as
+ * for kfmi_search_cpu), on the text as ASCII and a full suffix array of rows =
+ * n + 1 entries -- the one kfmi_device_jump_tables returns, or kfmi_index_sa at
+ * rate 1; entries >= rows are rows without a suffix.  It reads and writes the
+ * handles' host arrays and needs neither an index nor a device.
+ *   kfmi_results_to_device copies the host array of a results handle that is on
+ * a device (transferCPUtoGPU, which zeroes the device array and copies nothing
+ * up) to that device array: the way caller-filled `intervals` and `spans` reach
+ * the device.  KFMI_E_NOT_ON_DEVICE before the transfer, KFMI_E_NOT_IMPLEMENTED
+ * for device-group handles. */
+#define KFMI_HIT_NONE         0xFFFFFFFFu
+#define KFMI_HIT_MISM_MASK    0x0000FFFFu   /* y bits 0-15: mismatches of the reported hit            */
+#define KFMI_HIT_MULTI        0x00010000u   /* y bit 16: >= 2 distinct origins attain that count       */
+#define KFMI_HIT_SCORED_SHIFT 20            /* y bits 20-31: candidates scored (<= 8 * 256 = 2048)     */
+#define KFMI_VERIFY_MAX_OCC   256u
+int32_t kfmi_verify_seeds(void *index, void *queries, void *intervals, void *spans, void *hits,
+                          uint32_t max_seeds, uint32_t strands, uint32_t max_occ, uint32_t max_mism);
+int32_t kfmi_verify_seeds_cpu(const char *text, uint64_t n, const uint32_t *sa, uint64_t rows,
+                              void *queries, void *intervals, void *spans, void *hits,
+                              uint32_t max_seeds, uint32_t strands, uint32_t max_occ, uint32_t max_mism,
+                              int32_t nthreads);
+int32_t kfmi_results_to_device(void *results);
+
 /* ---- walk trace (tests and diagnosis; not in the reference, not timed) -------
  * The fused forward task kernel ends a walk early through three shortcuts --
  * the jump start, the skip table and the text jump (DESIGN.md 5a .. 5a''') --

@@ -1,0 +1,256 @@
+/*
+ * kfmi_verify.hip -- seed verification: the best Hamming placement of every
+ * task among the text positions its seeds imply (kstep_fmi.h section 2,
+ * "verify seeds"; not in the reference, which stops at
+ * intervals).
+ *
+ * Input: the reads on the device, the two handles a seed search leaves there
+ * (slot t * S + s: {L, R} in `intervals`, {start, len} in `spans`) and the flat
+ * tables [sa | isa | text] of the text jump (kfmi_jump.hip).  The FM index is
+ * never touched, so the kernel knows no geometry: it is templated on the code
+ * words per read (8 | 16) and on the staging (forward reads, or the strand
+ * staging for REV and BOTH) alone.
+ *
+ * One lane per task.  The lane packs its whole read into registers with the
+ * search's own packers -- rem = 0 whatever the index's K -- and walks its slots:
+ * rows L, L + 1, .. below min(R, rows, L + max_occ), each row r a candidate
+ * p = sa[r], origin o = p - start.  The read's code words and the text's word
+ * stream share their bit order (the base at reversed index r at bits 2r), so the
+ * window of origin o starts at bit 2 * (n - o - m) of the stream, takes
+ * ceil(m / 16) + 1 dwords, and the Hamming distance is an XOR, a mask on the
+ * last word and popc((x | x >> 1) & 0x55555555).
+ *
+ * A round is wave-uniform.  Every lane issues the window loads of the candidate
+ * it holds together with the sa load of its next row, then everything waits
+ * once: a candidate costs about one round trip.  Where the tables are past the
+ * translation reach (split_for(8 * rows, LAY_INTER) == 4, as for the jump's
+ * gathers) a lane's loads go out under its 16-lane group's mask.  Every address
+ * is in range before its load: rows below `rows`, window words clamped to the
+ * stream's last word.
+ */
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <mutex>
+#include <shared_mutex>
+
+#include "../kfmi_internal.h"
+#include "kfmi_device.h"
+#include "kfmi_runtime.h"
+
+namespace kfmi {
+
+struct VerifyArgs {
+  const uint8_t* __restrict__ ascii;   /* num reads of m bases */
+  const uint2* __restrict__ iv;        /* S slots per task: {L, R} */
+  const uint2* __restrict__ sp;        /* S slots per task: {start, len} */
+  uint2* __restrict__ hits;            /* one record per task */
+  const uint32_t* __restrict__ jsa;    /* [sa | isa | text] */
+  uint64_t num;
+  uint32_t m, strands, S, rows, max_occ, max_mism, split4;
+};
+
+/* STR: the strand staging (a.strands 2 = REV, 3 = BOTH: task 2q + strand), else forward reads. */
+template <int MAXW, bool STR>
+__global__ __launch_bounds__(256) void verify_kernel(VerifyArgs a)
+{
+  extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
+  uint32_t cw[MAXW];
+  if constexpr (STR) {
+    stage_strand_codes<MAXW>(a.ascii, a.num, a.m, stage, cw, a.strands);   /* whole block, before any exit */
+  } else {
+    uint32_t rc = 0;
+    stage_query_codes<MAXW>(a.ascii, a.num, a.m, stage, cw, 0u, rc);       /* whole block, before any exit */
+  }
+  const uint64_t t = (uint64_t) blockIdx.x * 256 + threadIdx.x;
+  if (t >= (STR && a.strands == 3u ? 2u : 1u) * a.num) return;
+  const uint32_t m = a.m, n = a.rows - 1u, nw = (m + 15u) >> 4;
+  const uint32_t* __restrict__ text = a.jsa + 2ull * a.rows;
+  const uint32_t wlast = (uint32_t) jump_text_words(n) - 1u;   /* the stream's last word */
+  const uint2* __restrict__ ivt = a.iv + t * a.S;
+  const uint2* __restrict__ spt = a.sp + t * a.S;
+  const int grp = (int) (threadIdx.x & 63u) / 16;
+  uint32_t s = 0, r = 0, rend = 0, start = 0;   /* the next slot, and the rows left of the current one */
+  uint32_t p = 0, pstart = 0;                   /* the candidate in hand: its sa value and its slot's start */
+  bool have = false;
+  uint32_t best_m = 0xFFFFFFFFu, best_o = 0xFFFFFFFFu, multi = 0u, scored = 0u;
+  for (;;) {
+    /* lanes out of rows take their next slot; an ignored slot leaves them out of rows */
+    while (__ballot(r >= rend && s < a.S)) {
+      if (r >= rend && s < a.S) {
+        const uint2 lr = ivt[s], sl = spt[s];
+        ++s;
+        if (lr.y > lr.x && lr.x < a.rows && sl.y != 0u && (uint64_t) sl.x + sl.y <= m) {
+          const uint64_t cap = (uint64_t) lr.x + a.max_occ;
+          const uint32_t e = lr.y < a.rows ? lr.y : a.rows;
+          r = lr.x;
+          rend = cap < e ? (uint32_t) cap : e;
+          start = sl.x;
+        }
+      }
+    }
+    const bool more = r < rend;   /* r < rows */
+    if (!__ballot(more || have)) break;
+    const bool sc = have && p < a.rows && p >= pstart && (uint64_t) (p - pstart) + m <= n;
+    const uint32_t o = sc ? p - pstart : 0u;
+    const uint32_t off = sc ? n - o - m : 0u;   /* the window starts at bit 2 * off of the stream */
+    /* sc: n >= m, so wlast >= nw; a scored window ends inside the stream, the clamp never moves it */
+    const uint32_t w0 = sc ? ((off >> 4) + nw <= wlast ? off >> 4 : wlast - nw) : 0u;
+    const uint32_t sh = (off & 15u) * 2u;
+    const uint32_t lim = sc ? nw + 1u : 0u;
+    const uint32_t* tp = text + w0;
+    uint32_t tx[MAXW + 1];
+#pragma unroll
+    for (int j = 0; j <= MAXW; ++j) tx[j] = 0u;
+    uint32_t np = SKIP_NONE;
+    if (a.split4) {   /* wave-uniform: all of a lane's loads under its group's mask */
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+        if (grp == g) {
+#pragma unroll
+          for (int j = 0; j <= MAXW; ++j)
+            if ((uint32_t) j < lim) tx[j] = tp[j];
+          if (more) np = a.jsa[r];
+        }
+    } else {
+#pragma unroll
+      for (int j = 0; j <= MAXW; ++j)
+        if ((uint32_t) j < lim) tx[j] = tp[j];
+      if (more) np = a.jsa[r];
+    }
+    if (sc) {
+      uint32_t mm = 0u;
+#pragma unroll
+      for (int j = 0; j < MAXW; ++j)
+        if ((uint32_t) j < nw) {
+          const uint32_t left = 2u * m - 32u * (uint32_t) j;   /* bits of the read from this word on */
+          const uint32_t x = (cw[j] ^ __builtin_amdgcn_alignbit(tx[j + 1], tx[j], sh)) &
+                             (left >= 32u ? 0xFFFFFFFFu : (1u << left) - 1u);
+          mm += (uint32_t) __popc((x | (x >> 1)) & 0x55555555u);
+        }
+      ++scored;
+      if (mm < best_m) {
+        best_m = mm;
+        best_o = o;
+        multi = 0u;
+      } else if (mm == best_m && o != best_o) {   /* another origin with the same count */
+        multi = KFMI_HIT_MULTI;
+        best_o = o < best_o ? o : best_o;
+      }
+    }
+    have = more;
+    if (more) {
+      p = np;
+      pstart = start;
+      ++r;
+    }
+  }
+  const bool hit = scored != 0u && best_m <= a.max_mism;
+  a.hits[t] = hit ? make_uint2(best_o, best_m | multi | (scored << KFMI_HIT_SCORED_SHIFT))
+                  : make_uint2(KFMI_HIT_NONE, scored << KFMI_HIT_SCORED_SHIFT);
+}
+
+static hipError_t launch_verify(const VerifyArgs& a, hipStream_t st)
+{
+  const bool str = a.strands != KFMI_STRAND_FWD;
+  const uint64_t tasks = (a.strands == KFMI_STRAND_BOTH ? 2u : 1u) * a.num;
+  const dim3 grid((uint32_t) ((tasks + 255) / 256));
+  const size_t lds = 4 * (size_t) stage_slot_bytes(a.m);
+  if (a.m <= 128) {
+    if (str) hipLaunchKernelGGL((verify_kernel<8, true>), grid, dim3(256), lds, st, a);
+    else hipLaunchKernelGGL((verify_kernel<8, false>), grid, dim3(256), lds, st, a);
+  } else {
+    if (str) hipLaunchKernelGGL((verify_kernel<16, true>), grid, dim3(256), lds, st, a);
+    else hipLaunchKernelGGL((verify_kernel<16, false>), grid, dim3(256), lds, st, a);
+  }
+  return hipGetLastError();
+}
+
+/* The device copies the seed search covers: the per-lane kernels on the two
+ * plain-counter layouts at K <= 2 ("task", "task-mid") -- the copies the text
+ * jump builds its tables for. */
+static bool verify_supported(const kfmi_dev_index* di)
+{
+  return !is_coop(di->backend) && (di->layout == LAY_INTER || di->layout == LAY_MID) && di->K >= 1 && di->K <= 2;
+}
+
+/* The host array of a transferred results handle copied to its device array:
+ * caller-filled slots for kfmi_verify_seeds (transferCPUtoGPU zeroes the device
+ * array it allocates and copies nothing up). */
+extern "C" int32_t kfmi_results_to_device(void* results)
+{
+  kfmi_res_t* r = (kfmi_res_t*) results;
+  if (!r) return KFMI_E_BAD_ARGUMENT;
+  if (r->grp) return KFMI_E_NOT_IMPLEMENTED;
+  if (!r->d_results) return KFMI_E_NOT_ON_DEVICE;
+  DeviceGuard dg;
+  DevCtx* ctx = nullptr;
+  const int32_t err = ctx_for(r->d_device, &ctx);
+  if (err) return err;
+  HIP_OK(hipMemcpyAsync(r->d_results, r->h_results, 8ull * r->num, hipMemcpyHostToDevice, ctx->st));
+  HIP_OK(hipStreamSynchronize(ctx->st));
+  return KFMI_SUCCESS;
+}
+
+extern "C" int32_t kfmi_verify_seeds(void* index, void* queries, void* intervals, void* spans, void* hits,
+                                     uint32_t max_seeds, uint32_t strands, uint32_t max_occ, uint32_t max_mism)
+{
+  if (max_seeds < 1 || max_seeds > 8) return KFMI_E_BAD_ARGUMENT;
+  if (strands < KFMI_STRAND_FWD || strands > KFMI_STRAND_BOTH) return KFMI_E_BAD_ARGUMENT;
+  if (max_occ < 1 || max_occ > KFMI_VERIFY_MAX_OCC) return KFMI_E_BAD_ARGUMENT;
+  kfmi_fmi_t* f = (kfmi_fmi_t*) index;
+  kfmi_qrys_t* q = (kfmi_qrys_t*) queries;
+  kfmi_res_t* ri = (kfmi_res_t*) intervals;
+  kfmi_res_t* rs = (kfmi_res_t*) spans;
+  kfmi_res_t* rh = (kfmi_res_t*) hits;
+  if (!f || !q || !ri || !rs || !rh || ri == rs || rh == ri || rh == rs) return KFMI_E_BAD_ARGUMENT;
+  const uint64_t tasks = (strands == KFMI_STRAND_BOTH ? 2u : 1u) * q->num;
+  if (ri->num != max_seeds * tasks || rs->num != max_seeds * tasks || rh->num != tasks) return KFMI_E_BAD_ARGUMENT;
+  if (q->size < 1 || q->size > 256) return KFMI_E_BAD_ARGUMENT;
+  DeviceGuard dg;
+  std::shared_lock<RwLock> lk(index_lock(f));
+  if (f->grp || q->grp || ri->grp || rs->grp || rh->grp) return KFMI_E_NOT_IMPLEMENTED;
+  if (!f->dev || !q->dev || !ri->d_results || !rs->d_results || !rh->d_results) return KFMI_E_NOT_ON_DEVICE;
+  kfmi_dev_index* di = f->dev;
+  kfmi_dev_queries* dq = q->dev;
+  if (!verify_supported(di)) return KFMI_E_NOT_IMPLEMENTED;
+  if (!dq->ascii) return KFMI_E_NOT_IMPLEMENTED;   /* KFMI_UPLOAD=packed: no ASCII rows on the device */
+  if (dq->device != di->device || dq->num != q->num || dq->size != q->size) return KFMI_E_BAD_ARGUMENT;
+  if (ri->d_device != di->device || rs->d_device != di->device || rh->d_device != di->device)
+    return KFMI_E_BAD_ARGUMENT;
+  DevCtx* ctx = nullptr;
+  int32_t err = ctx_for(di->device, &ctx);
+  hipEvent_t* ev = err ? nullptr : thread_events(di->device);
+  hipStream_t st = err ? nullptr : thread_stream(di->device);
+  if (!err && (!ev || !st)) err = KFMI_E_NO_DEVICE;
+  if (err) return err;
+  /* the text jump's tables, built here where the copy has none -- the path
+   * kfmi_set_jump(1) takes at a first search, whatever this thread's setting */
+  IdxArgs ix = idx_args(di);
+  err = use_jump(di, st, ix, 1u);
+  if (err) return err;
+  if (!ix.jsa) return KFMI_E_NOT_IMPLEMENTED;   /* the index failed the tables' exactness check */
+  VerifyArgs a{};
+  a.ascii = dq->ascii;
+  a.iv = reinterpret_cast<const uint2*>(ri->d_results);
+  a.sp = reinterpret_cast<const uint2*>(rs->d_results);
+  a.hits = reinterpret_cast<uint2*>(rh->d_results);
+  a.jsa = ix.jsa;
+  a.num = dq->num;
+  a.m = dq->size;
+  a.strands = strands;
+  a.S = max_seeds;
+  a.rows = di->bwtsize;
+  a.max_occ = max_occ;
+  a.max_mism = max_mism;
+  a.split4 = split_for(8ull * di->bwtsize, LAY_INTER) == 4u ? 1u : 0u;
+  HIP_OK(hipEventRecord(ev[0], st));
+  HIP_OK(hipEventRecord(ev[1], st));
+  if (dq->num) HIP_OK(launch_verify(a, st));
+  HIP_OK(hipEventRecord(ev[2], st));
+  err = search_finish(st, ev, t_ms);
+  t_ms[0] = t_ms[2];   /* total, 0, the verify kernel: nothing is packed beforehand */
+  t_ms[1] = 0.0;
+  return err;
+}
+
+}  // namespace kfmi

@@ -160,6 +160,9 @@ def load() -> ctypes.CDLL:
         "kfmi_search_seeds": (i32, [vp, vp, vp, vp, u32, u32]),
         "kfmi_search_seeds_cpu": (i32, [vp, vp, vp, vp, u32, u32, i32]),
         "kfmi_search_trace": (i32, [vp, vp, vp, vp]),
+        "kfmi_results_to_device": (i32, [vp]),
+        "kfmi_verify_seeds": (i32, [vp, vp, vp, vp, vp, u32, u32, u32, u32]),
+        "kfmi_verify_seeds_cpu": (i32, [vp, u64, vp, u64, vp, vp, vp, vp, u32, u32, u32, u32, i32]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -947,6 +950,98 @@ def search_seeds_array(index: Index, reads: np.ndarray, backend: str | None = No
         q.close()
         iv.close()
         sp.close()
+
+
+HIT_NONE = 0xFFFFFFFF
+HIT_MISM_MASK = 0x0000FFFF
+HIT_MULTI = 0x00010000
+HIT_SCORED_SHIFT = 20
+VERIFY_MAX_OCC = 256
+
+
+def results_to_gpu(results: Results) -> None:
+    """kfmi_results_to_device: the handle's host array copied to its device
+    array (transfer_to_gpu zeroes that array and copies nothing up)."""
+    _check(load().kfmi_results_to_device(results.ptr), "kfmi_results_to_device")
+
+
+def verify_seeds(index: Index, queries: Queries, intervals: Results, spans: Results, hits: Results, max_seeds: int,
+                 strands: int, max_occ: int, max_mism: int) -> None:
+    """kfmi_verify_seeds: the best Hamming placement of every task among the
+    text positions its seed slots imply (`intervals` / `spans` as search_seeds
+    leaves them on the device, at most max_occ rows per slot).  Entry t of
+    `hits` (ns * num entries, on the device): x = the origin or HIT_NONE, y =
+    mismatches | HIT_MULTI | scored << HIT_SCORED_SHIFT."""
+    _check(load().kfmi_verify_seeds(index.ptr, queries.ptr, intervals.ptr, spans.ptr, hits.ptr, int(max_seeds),
+                                    int(strands), int(max_occ), int(max_mism)), "kfmi_verify_seeds")
+
+
+def verify_seeds_cpu(text, sa: np.ndarray, queries: Queries, intervals: Results, spans: Results, hits: Results,
+                     max_seeds: int, strands: int, max_occ: int, max_mism: int, nthreads: int = 0) -> None:
+    """kfmi_verify_seeds_cpu: the same records on the host, from the text
+    (bytes or uint8 array of n bases) and its full suffix array (uint32
+    [n + 1], row 0 the '$' suffix) and the handles' host arrays."""
+    t = np.ascontiguousarray(np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text,
+                             dtype=np.uint8)
+    sa = np.ascontiguousarray(sa, dtype=np.uint32)
+    _check(load().kfmi_verify_seeds_cpu(t.ctypes.data_as(ctypes.c_void_p), t.size, sa.ctypes.data_as(ctypes.c_void_p),
+                                        sa.size, queries.ptr, intervals.ptr, spans.ptr, hits.ptr, int(max_seeds),
+                                        int(strands), int(max_occ), int(max_mism), int(nthreads)),
+           "kfmi_verify_seeds_cpu")
+
+
+def decode_hits(hits: np.ndarray):
+    """(origin int64 with -1 for none, mism, multi, scored) of uint32 [T, 2] hit records."""
+    h = np.asarray(hits, dtype=np.uint32).reshape(-1, 2)
+    x, y = h[:, 0].astype(np.int64), h[:, 1].astype(np.int64)
+    none = x == HIT_NONE
+    return (np.where(none, -1, x), np.where(none, 0, y & HIT_MISM_MASK), ((y & HIT_MULTI) != 0) & ~none,
+            y >> HIT_SCORED_SHIFT)
+
+
+def map_reads_array(index: Index, reads: np.ndarray, backend: str | None = None, max_seeds: int = 4,
+                    strands: int = STRAND_BOTH, max_occ: int = 8, max_mism: int | None = None, cpu: bool = False,
+                    text=None):
+    """Upload, seed search and verify of uint8 [N, m] reads in one call: where
+    each task maps and with how many differences.  Returns (origin, mism, multi,
+    scored), arrays of ns * N tasks (BOTH: task 2q + strand): origin -1 and
+    mism 0 where no scored candidate has at most max_mism mismatches (None:
+    no bound).  cpu=True runs both steps on the host and needs `text`, the
+    indexed text; the suffix array is the index's own at sampling rate 1, else
+    that of a temporary index of `text`."""
+    n, s = reads.shape[0], int(max_seeds)
+    ns = _strand_count(strands)
+    mm = 0xFFFFFFFF if max_mism is None else int(max_mism)
+    if backend and not cpu:
+        set_backend(backend)
+    q = Queries.from_array(reads)
+    iv, sp, hits = Results.alloc(max(s, 0) * ns * n), Results.alloc(max(s, 0) * ns * n), Results.alloc(ns * n)
+    tmp = None
+    try:
+        if cpu:
+            if text is None:
+                raise ValueError("map_reads_array(cpu=True) needs the indexed text")
+            rate, sa = index.sa()
+            if rate != 1:
+                tmp = Index.build(bytes(text), k=1, d=64, sa_rate=1)
+                rate, sa = tmp.sa()
+            search_seeds_cpu(index, q, iv, sp, s, strands)
+            verify_seeds_cpu(text, sa, q, iv, sp, hits, s, strands, max_occ, mm)
+        else:
+            transfer_to_gpu(index, q, iv)
+            transfer_to_gpu(index, None, sp)
+            transfer_to_gpu(index, None, hits)
+            search_seeds(index, q, iv, sp, s, strands)
+            verify_seeds(index, q, iv, sp, hits, s, strands, max_occ, mm)
+            transfer_to_cpu(hits)
+        return decode_hits(hits.array().copy())
+    finally:
+        if tmp is not None:
+            tmp.close()
+        q.close()
+        iv.close()
+        sp.close()
+        hits.close()
 
 
 def env_int(name: str, default: int) -> int:
