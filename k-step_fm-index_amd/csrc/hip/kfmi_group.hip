@@ -242,15 +242,13 @@ int32_t group_transfer(kfmi_fmi_t* f, kfmi_qrys_t* q, kfmi_res_t* r, const int* 
           (void) hipSetDevice(devs[i]);
           if (hipStreamSynchronize(g->st[i]) != hipSuccess && !err) err = KFMI_E_KERNEL;
         }
-      /* the auto jump-start table of every replica, built on its own device
-       * from its own copy (part of the upload, as on a single device) */
-      if (ftab_bases() == KFMI_FTAB_AUTO)
-        for (int i = 0; i < n && !err; ++i) {
-          if (hipSetDevice(devs[i]) != hipSuccess) err = KFMI_E_NO_DEVICE;
-          if (!err) err = auto_ftab(g->di[i], g->st[i], nullptr);
-          if (!err && skip_wanted() == 2u) err = auto_skip(g->di[i], g->st[i]);
-          if (!err && jump_wanted() == 2u) err = auto_jump(g->di[i], g->st[i]);
-        }
+      /* the auto tables of every replica, built on its own device from its own
+       * copy (part of the upload, as on a single device) */
+      const TableWants want = tables_wanted();
+      for (int i = 0; i < n && !err; ++i) {
+        if (hipSetDevice(devs[i]) != hipSuccess) err = KFMI_E_NO_DEVICE;
+        if (!err) err = auto_tables(g->di[i], g->st[i], want);
+      }
       if (err) {
         group_free_index(f);
         return err;
@@ -342,7 +340,7 @@ int32_t group_search(kfmi_fmi_t* f, kfmi_qrys_t* q, kfmi_res_t* r)
   if (gq->n != gi->n || gr->n != gi->n) return KFMI_E_BAD_ARGUMENT;
   for (int i = 0; i < gi->n; ++i)
     if (gq->dev[i] != gi->dev[i] || gr->dev[i] != gi->dev[i] || gq->num[i] != gr->num[i]) return KFMI_E_BAD_ARGUMENT;
-  const uint32_t ftab = ftab_bases(), skip = tables_wanted();
+  const TableWants want = tables_wanted();   /* the caller's, for every member */
   int32_t err = KFMI_SUCCESS;
   int queued = 0;
   for (int i = 0; i < gi->n && !err; ++i) {
@@ -350,7 +348,7 @@ int32_t group_search(kfmi_fmi_t* f, kfmi_qrys_t* q, kfmi_res_t* r)
       err = KFMI_E_NO_DEVICE;
       break;
     }
-    err = search_enqueue(gi->di[i], gq->dq[i], gr->d_res[i], gi->st[i], gi->ev[i], ftab, skip);
+    err = search_enqueue(gi->di[i], gq->dq[i], gr->d_res[i], gi->st[i], gi->ev[i], want);
     if (!err) ++queued;
   }
   double worst[3] = {0, 0, 0};

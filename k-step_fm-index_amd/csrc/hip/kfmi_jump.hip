@@ -2,8 +2,9 @@
  * kfmi_jump.hip -- the text jump's tables (DESIGN.md 5a'', kstep_fmi.h): per
  * device copy the full suffix array sa[row], its inverse isa[pos] and the
  * text's 2-bit codes laid out as the walk's code stream, built from the
- * uploaded index alone; the setting, the auto rule and the accessors.  The
- * kernel side is skip_walk<.., JUMP = true> (kfmi_kernels.h).
+ * uploaded index alone; the auto rule, jump_min and the accessors (the setting
+ * is with the other tables' in kfmi_tables.hip).  The kernel side is
+ * skip_walk<.., JUMP = true> (kfmi_kernels.h).
  *
  * Build.  lf_next_kernel gives next[i] = LF_K(i), a '$' row D_s its own
  * successor.  Every chain of a text's index ends at a row D_s, the row of
@@ -32,7 +33,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
-#include <string.h>
 #include <atomic>
 #include <mutex>
 #include <shared_mutex>
@@ -43,36 +43,8 @@
 
 namespace kfmi {
 
-static thread_local int t_jump = -1;   /* -1: KFMI_JUMP, else auto; 0 off, 1 on, 2: auto (kfmi_set_jump) */
 static std::atomic<uint32_t> g_jump_min{KFMI_JUMP_MIN_DEFAULT};
 static std::atomic<int> g_jump_lines{-1};   /* -1: KFMI_JUMP_LINES, else 1; kfmi_set_jump_lines */
-
-extern "C" int32_t kfmi_set_jump(uint32_t mode)
-{
-  if (mode > 1 && mode != KFMI_JUMP_AUTO) return KFMI_E_BAD_ARGUMENT;
-  t_jump = mode == KFMI_JUMP_AUTO ? 2 : (int) mode;
-  return KFMI_SUCCESS;
-}
-
-/* 0 = off, 1 = on (explicit), 2 = auto and in effect: exactly when the skip
- * setting is auto and in effect, so kfmi_set_ftab(0), KFMI_SKIP=0 and an
- * explicit ftab count keep naming the walks they always named. */
-uint32_t jump_wanted(void)
-{
-  int v = t_jump;
-  if (v < 0) {
-    static const int env = [] {   /* KFMI_JUMP, read once per process */
-      const char* e = getenv("KFMI_JUMP");
-      if (!e || !*e || !strcmp(e, "auto")) return 2;
-      return atoi(e) ? 1 : 0;
-    }();
-    v = env;
-  }
-  if (v == 2) return skip_wanted() == 2u ? 2u : 0u;
-  return (uint32_t) v;
-}
-
-extern "C" uint32_t kfmi_jump_in_effect(void) { return jump_wanted(); }
 
 extern "C" int32_t kfmi_set_jump_min(uint32_t bases)
 {
@@ -316,8 +288,8 @@ static int32_t build_jump(kfmi_dev_index* di, hipStream_t st)
   return done(KFMI_SUCCESS);
 }
 
-/* The auto tables of an index, decided once per device copy after its auto
- * skip table: built when kfmi_jump_auto says their peak fits the budget -- a
+/* The auto tables of an index, decided once per device copy, at an upload
+ * after its auto skip table (use_tables decides them before it): built when kfmi_jump_auto says their peak fits the budget -- a
  * quarter of the device memory free right now, or kfmi_set_ftab_budget's
  * bytes.  Never an allocation error. */
 int32_t auto_jump(kfmi_dev_index* di, hipStream_t st)
@@ -334,7 +306,7 @@ int32_t auto_jump(kfmi_dev_index* di, hipStream_t st)
 }
 
 /* Sets ix.jsa .. for a search under the caller's resolved setting
- * (jump_wanted): 2 = the auto tables if this copy has them, 1 = built now if
+ * (TableWants::jump): 2 = the auto tables if this copy has them, 1 = built now if
  * they are not there (an index that fails the exactness check still has none). */
 int32_t use_jump(kfmi_dev_index* di, hipStream_t st, IdxArgs& ix, uint32_t want)
 {
@@ -375,21 +347,6 @@ static uint64_t jump_line_bytes_of(kfmi_dev_index* di)
   return di->jump_sa ? 4ull * JUMP_LINE_DW * jump_line_count(di->bwtsize - 1) : 0ull;
 }
 
-static uint64_t sum_members(void* index, uint64_t (*of)(kfmi_dev_index*))
-{
-  kfmi_fmi_t* f = (kfmi_fmi_t*) index;
-  if (!f) return 0;
-  std::shared_lock<RwLock> lk(index_lock(f));
-  uint64_t b = 0;
-  if (f->grp) {
-    const GroupIndex* g = (const GroupIndex*) f->grp;
-    for (int i = 0; i < g->n; ++i) b += of(g->di[i]);
-  } else if (f->dev) {
-    b = of(f->dev);
-  }
-  return b;
-}
-
 extern "C" uint64_t kfmi_device_jump_bytes(void* index) { return sum_members(index, jump_bytes_of); }
 
 /* the line table's bytes, which kfmi_device_jump_bytes does not count */
@@ -406,15 +363,9 @@ extern "C" int32_t kfmi_device_jump_tables(void* index, uint32_t member, uint32_
   if (!f || !sa || !isa || !text) return KFMI_E_BAD_ARGUMENT;
   DeviceGuard dg;
   std::shared_lock<RwLock> lk(index_lock(f));
-  kfmi_dev_index* di = f->dev;
-  if (f->grp) {
-    const GroupIndex* g = (const GroupIndex*) f->grp;
-    if ((int) member >= g->n) return KFMI_E_BAD_ARGUMENT;
-    di = g->di[member];
-  } else if (member) {
-    return KFMI_E_BAD_ARGUMENT;
-  }
-  if (!di) return KFMI_E_NOT_ON_DEVICE;
+  kfmi_dev_index* di = nullptr;
+  const int32_t e = member_index(f, member, &di);
+  if (e) return e;
   std::lock_guard<std::mutex> tl(di->ftab_mu);
   if (!di->jump_sa) return KFMI_E_NOT_ON_DEVICE;
   if (rows != di->bwtsize || words != text_words(di->bwtsize - 1)) return KFMI_E_BAD_ARGUMENT;
@@ -433,15 +384,9 @@ extern "C" int32_t kfmi_device_jump_lines(void* index, uint32_t member, uint32_t
   if (!f || !out) return KFMI_E_BAD_ARGUMENT;
   DeviceGuard dg;
   std::shared_lock<RwLock> lk(index_lock(f));
-  kfmi_dev_index* di = f->dev;
-  if (f->grp) {
-    const GroupIndex* g = (const GroupIndex*) f->grp;
-    if ((int) member >= g->n) return KFMI_E_BAD_ARGUMENT;
-    di = g->di[member];
-  } else if (member) {
-    return KFMI_E_BAD_ARGUMENT;
-  }
-  if (!di) return KFMI_E_NOT_ON_DEVICE;
+  kfmi_dev_index* di = nullptr;
+  const int32_t e = member_index(f, member, &di);
+  if (e) return e;
   std::lock_guard<std::mutex> tl(di->ftab_mu);
   if (!di->jump_sa) return KFMI_E_NOT_ON_DEVICE;
   if (lines != jump_line_count(di->bwtsize - 1)) return KFMI_E_BAD_ARGUMENT;

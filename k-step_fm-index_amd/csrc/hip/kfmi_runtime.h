@@ -1,8 +1,10 @@
 /*
  * kfmi_runtime.h -- host-side runtime shared by the library's translation
- * units: kfmi_search.hip (backends, devices, uploads, the reference's entry
- * points), kfmi_group.hip (device groups), kfmi_locate.hip (locate) and
- * kfmi_stream.hip (streamed search, host worker pool).
+ * units: kfmi_search.hip (backends, devices, uploads, the walk check, the
+ * reference's entry points), kfmi_tables.hip and kfmi_jump.hip (the derived
+ * tables and their settings), kfmi_group.hip (device groups), kfmi_locate.hip
+ * (locate), kfmi_strands.hip / kfmi_seeds.hip / kfmi_verify.hip (strand and
+ * seed searches) and kfmi_stream.hip (streamed search, host worker pool).
  */
 #ifndef KFMI_RUNTIME_H_
 #define KFMI_RUNTIME_H_
@@ -135,15 +137,20 @@ hipError_t upload_staging(DevCtx* ctx, uint64_t need);
 int32_t ctx_for(int dev, DevCtx** out);   /* selects `dev`, creates its stream once */
 /* The calling thread's three timing events on device `dev` (current device). */
 hipEvent_t* thread_events(int dev);
-/* The calling thread's search stream on device `dev` (current device). */
-hipStream_t thread_stream(int dev);
+/* The calling thread's search lane on device `dev`, which becomes current: the
+ * device's context, the thread's own search stream and its timing events;
+ * ctx_for's error, or KFMI_E_NO_DEVICE when one of them cannot be created. */
+struct SearchLane {
+  DevCtx* ctx = nullptr;
+  hipStream_t st = nullptr;
+  hipEvent_t* ev = nullptr;
+};
+int32_t search_lane(int dev, SearchLane* lane);
 
 /* per calling thread (kfmi_search.hip) */
 extern thread_local int t_device;
 extern thread_local int32_t t_last_error;
 extern thread_local double t_ms[3];   /* kfmi_last_timing: total, pack, lf (ms) */
-uint32_t ftab_bases(void);
-uint32_t skip_wanted(void);   /* 0 off, 1 on, 2 auto and in effect (the ftab setting is auto too) */
 
 /* backends and kernel dispatch (kfmi_search.hip) */
 bool is_coop(int backend);
@@ -153,38 +160,46 @@ int32_t check_lf_walks(kfmi_dev_index* di, hipStream_t st);   /* sets di->lf_per
 hipError_t dispatch(Op op, uint32_t K, uint32_t nb, int lay, const SearchLaunch& a,
                     unsigned long long* d_total = nullptr);
 IdxArgs idx_args(const kfmi_dev_index* di);
-int32_t use_ftab(kfmi_dev_index* di, hipStream_t st, IdxArgs& ix, uint32_t bases);
-/* decides and builds the index's auto table once (device `di->device` current);
- * *bases (may be null) = its base count, 0 when it has none */
-int32_t auto_ftab(kfmi_dev_index* di, hipStream_t st, uint32_t* bases);
+/* per-lane gathers of a table of this size as lane groups: 4, 2 or 1 (KFMI_SPLIT answers instead) */
+uint32_t split_for(uint64_t table_bytes, int layout);
+hipError_t launch_pack(const kfmi_dev_queries* dq, hipStream_t st);
+
+/* the derived tables (kfmi_tables.hip): the calling thread's settings, resolved
+ * against each other -- ftab: a base count, 0 or KFMI_FTAB_AUTO; skip and jump:
+ * 0 off, 1 on, 2 auto and in effect (skip: the ftab setting is auto too; jump:
+ * skip is 2).  Taken once on the caller's thread and passed down (a group's or
+ * stream's member threads have their own); a search form that never takes the
+ * text jump says so where it takes the value: no_jump(). */
+struct TableWants {
+  uint32_t ftab = 0, skip = 0, jump = 0;
+  TableWants no_jump() const { return TableWants{ftab, skip, 0u}; }
+};
+TableWants tables_wanted(void);
+/* ix's tables for one search under `w` with reads of m % K = rem, built where
+ * `w` asks for one the copy does not have (the remainder table clears the ftab) */
+int32_t use_tables(kfmi_dev_index* di, hipStream_t st, IdxArgs& ix, const TableWants& w, uint32_t rem);
+/* an upload's part: the tables of a new device copy (`di->device` current) whose
+ * setting in `w` is auto; never an error when one does not fit */
+int32_t auto_tables(kfmi_dev_index* di, hipStream_t st, const TableWants& w);
 /* frees the tables of a device copy about to be replaced (handle locked exclusively) */
 void drop_ftabs(kfmi_dev_index* di);
-/* the skip table: the auto one, decided and built once per device copy (never
- * an error when it does not fit), and ix.skip for a search under `want` =
- * the caller's skip_wanted() */
-int32_t auto_skip(kfmi_dev_index* di, hipStream_t st);
-int32_t use_skip(kfmi_dev_index* di, hipStream_t st, IdxArgs& ix, uint32_t want);
-/* the text jump (kfmi_jump.hip): the caller's setting (0 off, 1 on, 2 auto and
- * in effect: exactly when skip_wanted() is 2), the auto tables of a device copy
- * (never an error when they do not fit or the index fails the check), ix.jsa
- * for a search, and the tables' release (caller holds ftab_mu or the handle's
- * exclusive lock).  A search's `skip` argument carries both settings:
- * tables_wanted() = skip_wanted() | jump_wanted() << 4, taken apart by use_skip;
- * the strand and seed searches pass skip_wanted() alone and never jump. */
-uint32_t jump_wanted(void);
-inline uint32_t tables_wanted(void) { return skip_wanted() | (jump_wanted() << 4); }
+/* the tables' budget now: kfmi_set_ftab_budget's bytes, or a quarter of the free memory of the current device */
+uint64_t table_budget_now(void);
+/* layouts that take the remainder table */
+bool rem_supported(int layout);
+/* `of` summed over a handle's device copies (every member of its device group,
+ * or the single copy) under its shared lock, and member `member` of them
+ * (member 0 = the single copy; caller holds the lock) */
+uint64_t sum_members(void* index, uint64_t (*of)(kfmi_dev_index*));
+int32_t member_index(const kfmi_fmi_t* f, uint32_t member, kfmi_dev_index** di);
+/* the text jump (kfmi_jump.hip), for use_tables and auto_tables: the auto tables
+ * of a device copy (never an error when they do not fit or the index fails the
+ * check), ix.jsa for a search under the resolved setting `want` (kfmi_verify_seeds
+ * calls it with 1 itself), and the tables' release (caller holds ftab_mu or the
+ * handle's exclusive lock) */
 int32_t auto_jump(kfmi_dev_index* di, hipStream_t st);
 int32_t use_jump(kfmi_dev_index* di, hipStream_t st, IdxArgs& ix, uint32_t want);
 void free_jump(kfmi_dev_index* di);
-/* per-lane gathers of a table of this size as lane groups: 4, 2 or 1 (KFMI_SPLIT answers instead) */
-uint32_t split_for(uint64_t table_bytes, int layout);
-/* the tables' budget now: kfmi_set_ftab_budget's bytes, or a quarter of the free memory of the current device */
-uint64_t table_budget_now(void);
-/* reads with m % K = rem != 0: layouts that take the remainder
- * table, and the table of an index (built on first use; clears the ftab) */
-bool rem_supported(int layout);
-int32_t use_rtab(kfmi_dev_index* di, hipStream_t st, IdxArgs& ix, uint32_t rem);
-hipError_t launch_pack(const kfmi_dev_queries* dq, hipStream_t st);
 
 /* uploads (kfmi_search.hip) */
 int32_t upload_index(kfmi_fmi_t* f, int backend, int dev, DevCtx* ctx, kfmi_dev_index** out = nullptr);
@@ -203,7 +218,7 @@ hipError_t h2d(void* dst, const void* src, uint64_t bytes, hipStream_t st);
 /* one device batch: queue pack + LF bracketed by ev[0..2], then wait (kfmi_search.hip) */
 /* trace: null, or num records on the device (kfmi_search_trace: the traced kernels, Op::Trace) */
 int32_t search_enqueue(kfmi_dev_index* di, kfmi_dev_queries* dq, uint32_t* d_res, hipStream_t st, hipEvent_t* ev,
-                       uint32_t ftab, uint32_t skip, uint4* trace = nullptr);
+                       const TableWants& want, uint4* trace = nullptr);
 int32_t search_finish(hipStream_t st, hipEvent_t* ev, double* ms);
 
 /* strand searches (kfmi_strands.hip): dq->strand_words sized for both strands

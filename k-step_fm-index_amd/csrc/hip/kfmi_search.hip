@@ -4,9 +4,10 @@
  * kernel dispatch tables, and the reference's GPU plugin entry points
  * (common/interface.h:36-41): transferCPUtoGPU, searchIndexGPU,
  * transferGPUtoCPU, free*GPU.  The kernels are in kfmi_kernels.h /
- * kfmi_coop.h / kfmi_locate.h (instantiated in kfmi_inst_*.hip); device
- * groups, locate and streaming in kfmi_group.hip, kfmi_locate.hip and
- * kfmi_stream.hip.
+ * kfmi_coop.h / kfmi_locate.h (instantiated in kfmi_inst_*.hip); the tables
+ * derived from an uploaded index and their settings in kfmi_tables.hip and
+ * kfmi_jump.hip; device groups, locate and streaming in kfmi_group.hip,
+ * kfmi_locate.hip and kfmi_stream.hip.
  *
  * Semantics: results are bit-identical to the reference CPU searchers
  * (fmIndexCPUBaseline.c:157-292 for task/coop/mid, -AltCounters.c:145-310
@@ -42,8 +43,6 @@ static thread_local bool t_backend_implicit = true;   /* neither KFMI_BACKEND no
 thread_local int t_device = -1;
 thread_local int32_t t_last_error = KFMI_SUCCESS;
 thread_local double t_ms[3] = {0, 0, 0};
-static thread_local int t_ftab = -1;   /* ftab bases; -1: KFMI_FTAB, else auto; -2: auto (kfmi_set_ftab) */
-static thread_local int t_skip = -1;   /* skip table; -1: KFMI_SKIP, else auto; 0 off, 1 on, 2: auto (kfmi_set_skip) */
 
 static int backend_from_name(const char* n)
 {
@@ -139,82 +138,6 @@ RwLock& index_lock(const void* f)
 }
 
 extern "C" void kfmi_set_last_error(int32_t e) { t_last_error = e; }
-
-extern "C" int32_t kfmi_set_ftab(uint32_t bases)
-{
-  if (bases > 16 && bases != KFMI_FTAB_AUTO) return KFMI_E_BAD_ARGUMENT;
-  t_ftab = bases == KFMI_FTAB_AUTO ? -2 : (int) bases;
-  return KFMI_SUCCESS;
-}
-
-/* The calling thread's setting: a base count, 0 (off) or KFMI_FTAB_AUTO, which
- * use_ftab resolves per index. */
-uint32_t ftab_bases(void)
-{
-  if (t_ftab >= 0) return (uint32_t) t_ftab;
-  if (t_ftab == -2) return KFMI_FTAB_AUTO;
-  static const uint32_t env = [] {   /* KFMI_FTAB, read once per process */
-    const char* e = getenv("KFMI_FTAB");
-    if (!e || !*e || !strcmp(e, "auto")) return (uint32_t) KFMI_FTAB_AUTO;
-    const int v = atoi(e);
-    return v > 0 && v <= 16 ? (uint32_t) v : 0u;
-  }();
-  return env;
-}
-
-/* The auto rule (kstep_fmi.h): host arithmetic only, so a CPU test calls it. */
-extern "C" uint32_t kfmi_ftab_auto_bases(uint64_t rows, uint32_t K, uint64_t budget_bytes)
-{
-  if (K < 1 || K > 4 || rows < 8) return 0;
-  uint32_t n = 16 - 16 % K;
-  while (n && (1ull << (2 * n)) > 2 * rows) n -= K;
-  while (n && (8ull << (2 * n)) > budget_bytes) n -= K;
-  return n;
-}
-
-extern "C" int32_t kfmi_set_skip(uint32_t mode)
-{
-  if (mode > 1 && mode != KFMI_SKIP_AUTO) return KFMI_E_BAD_ARGUMENT;
-  t_skip = mode == KFMI_SKIP_AUTO ? 2 : (int) mode;
-  return KFMI_SUCCESS;
-}
-
-/* The calling thread's skip-table setting resolved against its ftab setting
- * (kstep_fmi.h): 0 = off, 1 = on (kfmi_set_skip(1) / KFMI_SKIP=1: built at the
- * first search, an allocation failure is an error), 2 = auto and in effect --
- * exactly when the ftab setting is auto as well, so an explicit kfmi_set_ftab
- * (0 or N) keeps naming the walk it always named. */
-uint32_t skip_wanted(void)
-{
-  int v = t_skip;
-  if (v < 0) {
-    static const int env = [] {   /* KFMI_SKIP, read once per process */
-      const char* e = getenv("KFMI_SKIP");
-      if (!e || !*e || !strcmp(e, "auto")) return 2;
-      return atoi(e) ? 1 : 0;
-    }();
-    v = env;
-  }
-  if (v == 2) return ftab_bases() == KFMI_FTAB_AUTO ? 2u : 0u;
-  return (uint32_t) v;
-}
-
-extern "C" uint32_t kfmi_skip_in_effect(void) { return skip_wanted(); }
-
-/* The auto rule (kstep_fmi.h): host arithmetic only, so a CPU test calls it. */
-extern "C" uint32_t kfmi_skip_auto(uint64_t rows, uint32_t K, uint64_t budget_bytes)
-{
-  if (K < 1 || K > 2 || rows < 8 || rows > 0xFFFFFFFFull) return 0;
-  return 16 * rows <= budget_bytes ? 1u : 0u;
-}
-
-static std::atomic<uint64_t> g_ftab_budget{KFMI_FTAB_BUDGET_FREE};
-
-extern "C" int32_t kfmi_set_ftab_budget(uint64_t bytes)
-{
-  g_ftab_budget.store(bytes, std::memory_order_relaxed);
-  return KFMI_SUCCESS;
-}
 
 /* Test knobs of the search path: read from the environment once per process
  * (KFMI_SPLIT, KFMI_FUSED) and switched through their setters afterwards, so
@@ -323,12 +246,21 @@ hipEvent_t* thread_events(int dev)
   return ev;
 }
 
-hipStream_t thread_stream(int dev)
+static hipStream_t thread_stream(int dev)
 {
   if (dev < 0 || dev >= 64) return nullptr;
   if (!t_res.st[dev] && hipStreamCreateWithFlags(&t_res.st[dev], hipStreamNonBlocking) != hipSuccess)
     t_res.st[dev] = nullptr;
   return t_res.st[dev];
+}
+
+int32_t search_lane(int dev, SearchLane* lane)
+{
+  const int32_t err = ctx_for(dev, &lane->ctx);
+  if (err) return err;
+  lane->ev = thread_events(dev);
+  lane->st = thread_stream(dev);
+  return lane->ev && lane->st ? KFMI_SUCCESS : KFMI_E_NO_DEVICE;
 }
 
 /* ------------------------------------------------------------------------ */
@@ -1499,303 +1431,6 @@ int32_t check_lf_walks(kfmi_dev_index* di, hipStream_t st)
   return done(KFMI_SUCCESS);
 }
 
-/* Reads with m % K = rem != 0 (the reference reads P[-1] there, defect B6):
- * their last rem bases are resolved by the remainder table, built once per
- * (index, rem) from the uploaded layout (rem_tab_kernel), and the K-steps
- * cover bases 0 .. m-rem-1.  The result is the reads' suffix-array interval,
- * which is what every plain-semantics backend returns for m % K = 0; the
- * AltCounters-semantics backends keep rejecting such reads (their intervals
- * differ from the true ones where the reference's sentinel counts, and the
- * reference defines no result here).  The ftab is not combined with it. */
-bool rem_supported(int layout)
-{
-  return layout == LAY_INTER || layout == LAY_MID || layout == LAY_GRP;
-}
-
-int32_t use_rtab(kfmi_dev_index* di, hipStream_t st, IdxArgs& ix, uint32_t rem)
-{
-  ix.rtab = nullptr;
-  ix.rem = 0;
-  if (!rem) return KFMI_SUCCESS;
-  if (rem >= di->K || rem > 3 || !rem_supported(di->layout)) return KFMI_E_BAD_ARGUMENT;
-  {
-    std::lock_guard<std::mutex> lk(di->ftab_mu);
-    if (!di->rtab[rem]) {
-      uint2* t = nullptr;
-      if (hipMalloc((void**) &t, 8ull << (2 * rem)) != hipSuccess) return KFMI_E_DEVICE_ALLOC;
-      SearchLaunch a{};
-      a.st = st;
-      a.ix = idx_args(di);
-      a.ftab_out = t;
-      a.rem = rem;
-      if (dispatch(Op::RemTab, di->K, di->nb, di->layout, a) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        (void) hipFree(t);
-        return KFMI_E_KERNEL;
-      }
-      di->rtab[rem] = t;   /* published complete; never replaced */
-    }
-  }
-  ix.rtab = di->rtab[rem];
-  ix.rem = rem;
-  ix.ftab = nullptr;
-  ix.ftab_steps = 0;
-  ix.ftab_mask = 0;
-  return KFMI_SUCCESS;
-}
-
-/* The table of `bases` bases built into di->ftab[bases] (caller holds ftab_mu):
- * one launch per level on `st` (launch_ftab), waited for. */
-static int32_t build_ftab(kfmi_dev_index* di, hipStream_t st, uint32_t bases)
-{
-  uint2* t = nullptr;
-  if (hipMalloc((void**) &t, 8ull << (2 * bases)) != hipSuccess) {
-    (void) hipGetLastError();
-    return KFMI_E_DEVICE_ALLOC;
-  }
-  SearchLaunch a{};
-  a.st = st;
-  a.ix = idx_args(di);
-  a.ftab_out = t;
-  a.ftab_steps = bases / di->K;
-  a.ftab_n = 1ull << (2 * bases);
-  if (dispatch(Op::Ftab, di->K, di->nb, di->layout, a) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-    (void) hipFree(t);
-    return KFMI_E_KERNEL;
-  }
-  di->ftab[bases] = t;   /* published complete; never replaced */
-  return KFMI_SUCCESS;
-}
-
-/* The auto table of an index (KFMI_FTAB_AUTO), decided once per device copy:
- * kfmi_ftab_auto_bases of its rows, K and the budget -- a quarter of the
- * device memory free right now, or kfmi_set_ftab_budget's bytes -- and, when
- * that table cannot be allocated, K bases fewer until one can or none is left.
- * Never an allocation error: the search then walks every step.  Called from
- * the uploads (transferCPUtoGPU, group_transfer) when the caller's setting is
- * auto, so that no search pays for the build, and from use_ftab for an index
- * uploaded under another setting. */
-int32_t auto_ftab(kfmi_dev_index* di, hipStream_t st, uint32_t* bases)
-{
-  std::lock_guard<std::mutex> lk(di->ftab_mu);
-  if (di->ftab_auto < 0) {
-    uint64_t budget = g_ftab_budget.load(std::memory_order_relaxed);
-    if (budget == KFMI_FTAB_BUDGET_FREE) {
-      size_t free_b = 0, total_b = 0;
-      if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
-        (void) hipGetLastError();
-        free_b = 0;
-      }
-      budget = (uint64_t) free_b / 4;
-    }
-    uint32_t n = kfmi_ftab_auto_bases(di->bwtsize, di->K, budget);
-    for (; n; n -= di->K) {
-      if (di->ftab[n]) break;   /* an explicit setting built it already */
-      const int32_t e = build_ftab(di, st, n);
-      if (!e) break;
-      if (e != KFMI_E_DEVICE_ALLOC) return e;
-    }
-    di->ftab_auto = (int) n;
-  }
-  if (bases) *bases = (uint32_t) di->ftab_auto;
-  return KFMI_SUCCESS;
-}
-
-/* Skip table, doubling (the exactness argument: skip_level0_kernel): entry i of
- * 2s steps = entry i of s steps, then the entry of the row it ends in, whose
- * codes go `shift` = 2K*s bits above the first half's; invalid when either
- * half is.  The second lookup is a gather into a table that can lie past the
- * translation reach (24 GB at 3 Gbase): with `split` it is issued as four
- * exec-masked 16-lane groups, like the task kernels' index gathers.  Entry
- * loads are 8 bytes at 8-byte alignment, never wider (load_words' rule). */
-__global__ __launch_bounds__(256) void skip_double_kernel(const uint2* __restrict__ in, uint64_t rows, uint32_t shift,
-                                                          uint32_t split, uint2* __restrict__ out)
-{
-  const int grp = (int) (threadIdx.x & 63) / 16;
-  for (uint64_t i = (uint64_t) blockIdx.x * 256 + threadIdx.x; i < rows; i += (uint64_t) gridDim.x * 256) {
-    const uint2 a = in[i];
-    const bool ok = a.x != SKIP_NONE && (uint64_t) a.x < rows;
-    uint2 b = make_uint2(SKIP_NONE, 0u);
-    if (split) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-        if (ok && grp == g) b = in[a.x];
-    } else if (ok) {
-      b = in[a.x];
-    }
-    out[i] = (ok && b.x != SKIP_NONE) ? make_uint2(b.x, a.y | (b.y << shift)) : make_uint2(SKIP_NONE, 0u);
-  }
-}
-
-/* The skip table of a device copy built into di->skip (caller holds ftab_mu):
- * level 0 from the uploaded layout, then log2(16 / K) doublings between two
- * buffers; the second buffer is freed before returning.  KFMI_E_DEVICE_ALLOC
- * when the two buffers do not fit. */
-static int32_t build_skip(kfmi_dev_index* di, hipStream_t st)
-{
-  const uint64_t rows = di->bwtsize;
-  uint2* buf[2] = {nullptr, nullptr};
-  for (uint2*& b : buf)
-    if (hipMalloc((void**) &b, 8ull * rows) != hipSuccess) {
-      (void) hipGetLastError();
-      if (buf[0]) (void) hipFree(buf[0]);
-      return KFMI_E_DEVICE_ALLOC;
-    }
-  SearchLaunch a{};
-  a.st = st;
-  a.ix = idx_args(di);
-  a.num = rows;
-  a.skip_out = buf[0];
-  bool ok = dispatch(Op::Skip0, di->K, di->nb, di->layout, a) == hipSuccess;
-  const uint32_t J = 16u / di->K;
-  const uint32_t split = split_for(8ull * rows, LAY_INTER) == 4u ? 1u : 0u;
-  int cur = 0;
-  for (uint32_t s = 1; ok && s < J; s *= 2, cur ^= 1) {
-    hipLaunchKernelGGL(skip_double_kernel, dim3(grid_blocks((rows + 255) / 256, 1u << 20)), dim3(256), 0, st, buf[cur],
-                       rows, 2u * di->K * s, split, buf[cur ^ 1]);
-    ok = hipGetLastError() == hipSuccess;
-  }
-  ok = hipStreamSynchronize(st) == hipSuccess && ok;
-  (void) hipFree(buf[cur ^ 1]);
-  if (!ok) {
-    (void) hipFree(buf[cur]);
-    return KFMI_E_KERNEL;
-  }
-  di->skip = buf[cur];   /* published complete; never replaced */
-  return KFMI_SUCCESS;
-}
-
-/* Whether a device copy takes the skip table at all: the per-lane (task)
- * kernels at K <= 2.  The coop kernels, K = 3 / 4 and every non-search kernel
- * ignore it (DESIGN.md 5a'), so no table is built for them. */
-static bool skip_applies(const kfmi_dev_index* di)
-{
-  return di->K >= 1 && di->K <= 2 && !is_coop(di->backend) && di->layout != LAY_GRP;
-}
-
-uint64_t table_budget_now(void)
-{
-  uint64_t budget = g_ftab_budget.load(std::memory_order_relaxed);
-  if (budget == KFMI_FTAB_BUDGET_FREE) {
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
-      (void) hipGetLastError();
-      free_b = 0;
-    }
-    budget = (uint64_t) free_b / 4;
-  }
-  return budget;
-}
-
-/* The auto skip table of an index, decided once per device copy after its auto
- * ftab: built when kfmi_skip_auto says the table and its transient twin fit the
- * budget -- a quarter of the device memory free right now, or
- * kfmi_set_ftab_budget's bytes.  Never an error: without the table the search
- * walks every K-step. */
-int32_t auto_skip(kfmi_dev_index* di, hipStream_t st)
-{
-  std::lock_guard<std::mutex> lk(di->ftab_mu);
-  if (di->skip_auto >= 0 || di->skip) return KFMI_SUCCESS;
-  di->skip_auto = 0;
-  if (!skip_applies(di)) return KFMI_SUCCESS;
-  uint64_t budget = g_ftab_budget.load(std::memory_order_relaxed);
-  if (budget == KFMI_FTAB_BUDGET_FREE) {
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
-      (void) hipGetLastError();
-      free_b = 0;
-    }
-    budget = (uint64_t) free_b / 4;
-  }
-  if (!kfmi_skip_auto(di->bwtsize, di->K, budget)) return KFMI_SUCCESS;
-  const int32_t e = build_skip(di, st);
-  if (e && e != KFMI_E_DEVICE_ALLOC) return e;
-  di->skip_auto = e ? 0 : 1;
-  return KFMI_SUCCESS;
-}
-
-/* Sets ix.skip for a search under the caller's resolved setting (skip_wanted):
- * 2 = the auto table if this copy has one (decided here for a copy uploaded
- * under another setting), 1 = built now if it is not there. */
-int32_t use_skip(kfmi_dev_index* di, hipStream_t st, IdxArgs& ix, uint32_t want)
-{
-  const int32_t ej = use_jump(di, st, ix, want >> 4);   /* tables_wanted(): the text jump's setting rides above */
-  if (ej) return ej;
-  want &= 15u;
-  ix.skip = nullptr;
-  ix.skip_rows = 0;
-  ix.skip_steps = 0;
-  ix.skip_split = 1;
-  if (!want || !skip_applies(di)) return KFMI_SUCCESS;
-  if (want == 2) {
-    const int32_t e = auto_skip(di, st);
-    if (e) return e;
-  }
-  {
-    std::lock_guard<std::mutex> lk(di->ftab_mu);
-    if (!di->skip) {
-      if (want == 2) return KFMI_SUCCESS;
-      const int32_t e = build_skip(di, st);
-      if (e) return e;
-    }
-  }
-  ix.skip = di->skip;
-  ix.skip_rows = di->bwtsize;
-  ix.skip_steps = 16u / di->K;
-  ix.skip_split = split_for(8ull * di->bwtsize, LAY_INTER);
-  return KFMI_SUCCESS;
-}
-
-/* Frees the jump-start tables of a device copy that is about to be replaced
- * (caller holds the handle's exclusive lock: no search reads them).  They are
- * derived data, up to 34 GB each, and the replacing upload needs the memory:
- * a K = 4 copy re-laid for another backend holds two 96 GB layouts for a
- * moment.  Should that upload fail, the old copy stays searchable and builds
- * its tables again on demand -- except when it fails for lack of device
- * memory: then transferCPUtoGPU frees the old copy too and uploads again. */
-void drop_ftabs(kfmi_dev_index* di)
-{
-  if (!di) return;
-  std::lock_guard<std::mutex> lk(di->ftab_mu);
-  if (di->device >= 0) (void) hipSetDevice(di->device);
-  for (uint2*& t : di->ftab)
-    if (t) {
-      (void) hipFree(t);
-      t = nullptr;
-    }
-  di->ftab_auto = -1;
-  if (di->skip) (void) hipFree(di->skip);   /* the skip table goes with them */
-  di->skip = nullptr;
-  di->skip_auto = -1;
-  free_jump(di);   /* and the text jump's */
-}
-
-/* The ftab of `bases` bases (KFMI_FTAB_AUTO: the index's auto table), built
- * on the device from the uploaded layout with the search's own LF steps when
- * it is not there yet; sets ix.ftab (null when off or when bases is not a
- * multiple of K). */
-int32_t use_ftab(kfmi_dev_index* di, hipStream_t st, IdxArgs& ix, uint32_t bases)
-{
-  ix.ftab = nullptr;
-  ix.ftab_steps = 0;
-  ix.ftab_mask = 0;
-  if (bases == KFMI_FTAB_AUTO) {
-    const int32_t e = auto_ftab(di, st, &bases);
-    if (e) return e;
-  }
-  if (!bases || bases % di->K || bases > 16) return KFMI_SUCCESS;
-  {
-    std::lock_guard<std::mutex> lk(di->ftab_mu);
-    if (!di->ftab[bases]) {
-      const int32_t e = build_ftab(di, st, bases);
-      if (e) return e;
-    }
-  }
-  ix.ftab = di->ftab[bases];
-  ix.ftab_steps = bases / di->K;
-  ix.ftab_mask = bases >= 16 ? 0xFFFFFFFFu : (1u << (2 * bases)) - 1u;
-  return KFMI_SUCCESS;
-}
-
 void free_dev_queries(kfmi_dev_queries* dq)
 {
   if (!dq) return;
@@ -2028,10 +1663,8 @@ extern "C" int32_t transferCPUtoGPU(void* index, void* queries, void* results)
         /* a failed hipMalloc stays in the runtime's last error: left there, the next upload's
          * first launch check would read it as its own */
         if (err == KFMI_E_DEVICE_ALLOC) (void) hipGetLastError();
-        /* the auto jump-start table is part of the upload, like the re-layout */
-        if (!err && ftab_bases() == KFMI_FTAB_AUTO) err = auto_ftab(f->dev, ctx->st, nullptr);
-        if (!err && skip_wanted() == 2u) err = auto_skip(f->dev, ctx->st);   /* and the skip table after it */
-        if (!err && jump_wanted() == 2u) err = auto_jump(f->dev, ctx->st);   /* then the text jump's tables */
+        /* the auto tables are part of the upload, like the re-layout */
+        if (!err) err = auto_tables(f->dev, ctx->st, tables_wanted());
         if (err) return err;
       }
       qk = device_steps(f);
@@ -2076,15 +1709,13 @@ extern "C" int32_t transferCPUtoGPU(void* index, void* queries, void* results)
 /* Queues pack (if not fused) + LF of one device batch on `st`, bracketed by
  * ev[0..2]; search_finish waits and reads the timings. */
 int32_t search_enqueue(kfmi_dev_index* di, kfmi_dev_queries* dq, uint32_t* d_res, hipStream_t st,
-                              hipEvent_t* ev, uint32_t ftab, uint32_t skip, uint4* trace)
+                              hipEvent_t* ev, const TableWants& want, uint4* trace)
 {
   if (dq->device != di->device || dq->K != di->K) return KFMI_E_BAD_ARGUMENT;
   SearchLaunch a{};
   a.st = st;
   a.ix = idx_args(di);
-  int32_t err = use_ftab(di, st, a.ix, ftab);
-  if (!err) err = use_rtab(di, st, a.ix, dq->rem);
-  if (!err) err = use_skip(di, st, a.ix, skip);
+  const int32_t err = use_tables(di, st, a.ix, want, dq->rem);
   if (err) return err;
   a.qp = dq->packed;
   a.ascii = dq->ascii;
@@ -2132,13 +1763,10 @@ extern "C" int32_t kfmi_search(void* index, void* queries, void* results)
   if (!f->dev || !q->dev || !r->d_results) return KFMI_E_NOT_ON_DEVICE;
   kfmi_dev_index* di = f->dev;
   if (r->d_device != di->device) return KFMI_E_BAD_ARGUMENT;   /* handles transferred to different devices */
-  DevCtx* ctx = nullptr;
-  int32_t err = ctx_for(di->device, &ctx);
-  hipEvent_t* ev = err ? nullptr : thread_events(di->device);
-  hipStream_t st = err ? nullptr : thread_stream(di->device);
-  if (!err && (!ev || !st)) err = KFMI_E_NO_DEVICE;
-  if (!err) err = search_enqueue(di, q->dev, r->d_results, st, ev, ftab_bases(), tables_wanted());
-  if (!err) err = search_finish(st, ev, t_ms);
+  SearchLane l;
+  int32_t err = search_lane(di->device, &l);
+  if (!err) err = search_enqueue(di, q->dev, r->d_results, l.st, l.ev, tables_wanted());
+  if (!err) err = search_finish(l.st, l.ev, t_ms);
   return err;
 }
 
@@ -2163,19 +1791,16 @@ extern "C" int32_t kfmi_search_trace(void* index, void* queries, void* results, 
   if (is_coop(di->backend) || (di->layout != LAY_INTER && di->layout != LAY_MID) || di->K < 1 || di->K > 2)
     return KFMI_E_NOT_IMPLEMENTED;
   if (!dq->ascii || !fused_maxw(di->backend, dq->K * dq->steps)) return KFMI_E_NOT_IMPLEMENTED;
-  DevCtx* ctx = nullptr;
-  int32_t err = ctx_for(di->device, &ctx);
-  hipEvent_t* ev = err ? nullptr : thread_events(di->device);
-  hipStream_t st = err ? nullptr : thread_stream(di->device);
-  if (!err && (!ev || !st)) err = KFMI_E_NO_DEVICE;
+  SearchLane l;
+  int32_t err = search_lane(di->device, &l);
   if (err) return err;
   uint4* d_trace = nullptr;
   if (hipMalloc((void**) &d_trace, 16ull * (q->num ? q->num : 1)) != hipSuccess) {
     (void) hipGetLastError();
     return KFMI_E_DEVICE_ALLOC;
   }
-  err = search_enqueue(di, dq, r->d_results, st, ev, ftab_bases(), tables_wanted(), d_trace);
-  if (!err) err = search_finish(st, ev, t_ms);
+  err = search_enqueue(di, dq, r->d_results, l.st, l.ev, tables_wanted(), d_trace);
+  if (!err) err = search_finish(l.st, l.ev, t_ms);
   if (!err && q->num && hipMemcpy(trace, d_trace, 16ull * q->num, hipMemcpyDeviceToHost) != hipSuccess) err = KFMI_E_KERNEL;
   (void) hipFree(d_trace);
   return err;
@@ -2245,7 +1870,7 @@ static int32_t count_on(kfmi_dev_index* di, kfmi_dev_queries* dq, Op op, uint64_
   a.st = ctx->st;
   a.ix = idx_args(di);
   if (dq->device != di->device || dq->K != di->K) return KFMI_E_BAD_ARGUMENT;
-  err = use_rtab(di, ctx->st, a.ix, dq->rem);
+  err = use_tables(di, ctx->st, a.ix, TableWants{}, dq->rem);   /* the remainder table alone */
   if (err) return err;
   unsigned long long* d_total = nullptr;
   HIP_OK(hipMalloc((void**) &d_total, 4 * sizeof(unsigned long long)));
@@ -2340,82 +1965,7 @@ extern "C" int32_t freeResultsGPU(void** results)
 
 extern "C" uint64_t kfmi_device_index_bytes(void* index)
 {
-  kfmi_fmi_t* f = (kfmi_fmi_t*) index;
-  if (!f) return 0;
-  std::shared_lock<RwLock> lk(index_lock(f));
-  if (f->grp) {   /* all replicas of a device group */
-    const GroupIndex* g = (const GroupIndex*) f->grp;
-    uint64_t b = 0;
-    for (int i = 0; i < g->n; ++i) b += g->di[i]->ent_bytes + g->di[i]->sa_bytes;
-    return b;
-  }
-  if (!f || !f->dev) return 0;
-  return f->dev->ent_bytes + f->dev->sa_bytes;
-}
-
-static uint64_t ftab_bytes_of(kfmi_dev_index* di)
-{
-  std::lock_guard<std::mutex> lk(di->ftab_mu);
-  uint64_t b = 0;
-  for (uint32_t n = 1; n <= 16; ++n)
-    if (di->ftab[n]) b += 8ull << (2 * n);
-  return b;
-}
-
-static uint64_t skip_bytes_of(kfmi_dev_index* di)
-{
-  std::lock_guard<std::mutex> lk(di->ftab_mu);
-  return di->skip ? 8ull * di->bwtsize : 0ull;
-}
-
-extern "C" uint64_t kfmi_device_skip_bytes(void* index)
-{
-  kfmi_fmi_t* f = (kfmi_fmi_t*) index;
-  if (!f) return 0;
-  std::shared_lock<RwLock> lk(index_lock(f));
-  uint64_t b = 0;
-  if (f->grp) {
-    const GroupIndex* g = (const GroupIndex*) f->grp;
-    for (int i = 0; i < g->n; ++i) b += skip_bytes_of(g->di[i]);
-  } else if (f->dev) {
-    b = skip_bytes_of(f->dev);
-  }
-  return b;
-}
-
-/* Test accessor: the single-device copy's skip table copied to `out`
- * (`entries` uint2 {row, code}); KFMI_E_NOT_ON_DEVICE without a table,
- * KFMI_E_BAD_ARGUMENT when `entries` is not its row count. */
-extern "C" int32_t kfmi_device_skip_table(void* index, void* out, uint64_t entries, uint32_t* steps)
-{
-  kfmi_fmi_t* f = (kfmi_fmi_t*) index;
-  if (!f || !out) return KFMI_E_BAD_ARGUMENT;
-  DeviceGuard dg;
-  std::shared_lock<RwLock> lk(index_lock(f));
-  kfmi_dev_index* di = f->dev;
-  if (!di) return KFMI_E_NOT_ON_DEVICE;
-  std::lock_guard<std::mutex> tl(di->ftab_mu);
-  if (!di->skip) return KFMI_E_NOT_ON_DEVICE;
-  if (entries != di->bwtsize) return KFMI_E_BAD_ARGUMENT;
-  if (hipSetDevice(di->device) != hipSuccess) return KFMI_E_NO_DEVICE;
-  HIP_OK(hipMemcpy(out, di->skip, 8ull * entries, hipMemcpyDeviceToHost));
-  if (steps) *steps = 16u / di->K;
-  return KFMI_SUCCESS;
-}
-
-extern "C" uint64_t kfmi_device_ftab_bytes(void* index)
-{
-  kfmi_fmi_t* f = (kfmi_fmi_t*) index;
-  if (!f) return 0;
-  std::shared_lock<RwLock> lk(index_lock(f));
-  uint64_t b = 0;
-  if (f->grp) {
-    const GroupIndex* g = (const GroupIndex*) f->grp;
-    for (int i = 0; i < g->n; ++i) b += ftab_bytes_of(g->di[i]);
-  } else if (f->dev) {
-    b = ftab_bytes_of(f->dev);
-  }
-  return b;
+  return sum_members(index, [](kfmi_dev_index* di) { return di->ent_bytes + di->sa_bytes; });
 }
 
 }  // namespace kfmi

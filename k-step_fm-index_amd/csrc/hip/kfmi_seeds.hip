@@ -54,7 +54,7 @@ static bool seeds_supported(const kfmi_dev_index* di)
  * in the kernel where a strand search would (strand_fused_maxw), else walk
  * the strand pack's task columns. */
 static int32_t seeds_enqueue(kfmi_dev_index* di, kfmi_dev_queries* dq, uint32_t* d_iv, uint32_t* d_sp, hipStream_t st,
-                             hipEvent_t* ev, uint32_t ftab, uint32_t skip, uint32_t max_seeds, uint32_t strands,
+                             hipEvent_t* ev, const TableWants& want, uint32_t max_seeds, uint32_t strands,
                              DevCtx* ctx)
 {
   if (dq->device != di->device || dq->K != di->K) return KFMI_E_BAD_ARGUMENT;
@@ -63,9 +63,7 @@ static int32_t seeds_enqueue(kfmi_dev_index* di, kfmi_dev_queries* dq, uint32_t*
   SearchLaunch a{};
   a.st = st;
   a.ix = idx_args(di);
-  int32_t err = use_ftab(di, st, a.ix, ftab);
-  if (!err) err = use_rtab(di, st, a.ix, dq->rem);
-  if (!err) err = use_skip(di, st, a.ix, skip);
+  int32_t err = use_tables(di, st, a.ix, want, dq->rem);
   if (err) return err;
   if (fwd) a.maxw = dq->ascii ? fused_maxw(di->backend, dq->K * dq->steps) : 0;
   else a.maxw = strand_fused_maxw(di, dq->ascii != nullptr, dq->K, dq->steps, dq->rem);
@@ -116,15 +114,12 @@ extern "C" int32_t kfmi_search_seeds(void* index, void* queries, void* intervals
   kfmi_dev_index* di = f->dev;
   if (!seeds_supported(di)) return KFMI_E_NOT_IMPLEMENTED;
   if (ri->d_device != di->device || rs->d_device != di->device) return KFMI_E_BAD_ARGUMENT;
-  DevCtx* ctx = nullptr;
-  int32_t err = ctx_for(di->device, &ctx);
-  hipEvent_t* ev = err ? nullptr : thread_events(di->device);
-  hipStream_t st = err ? nullptr : thread_stream(di->device);
-  if (!err && (!ev || !st)) err = KFMI_E_NO_DEVICE;
-  if (!err)
-    err = seeds_enqueue(di, q->dev, ri->d_results, rs->d_results, st, ev, ftab_bases(), skip_wanted(), max_seeds,
-                        strands, ctx);
-  if (!err) err = search_finish(st, ev, t_ms);
+  SearchLane l;
+  int32_t err = search_lane(di->device, &l);
+  if (!err)   /* a seed search never takes the text jump */
+    err = seeds_enqueue(di, q->dev, ri->d_results, rs->d_results, l.st, l.ev, tables_wanted().no_jump(), max_seeds,
+                        strands, l.ctx);
+  if (!err) err = search_finish(l.st, l.ev, t_ms);
   return err;
 }
 

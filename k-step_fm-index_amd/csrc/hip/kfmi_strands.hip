@@ -288,7 +288,7 @@ int strand_fused_maxw(const kfmi_dev_index* di, bool ascii, uint32_t K, uint32_t
  * forward kernels run as they are; with the skip table in effect the task
  * backends walk the words with it, task_words_skip_kernel). */
 static int32_t strands_enqueue(kfmi_dev_index* di, kfmi_dev_queries* dq, uint32_t* d_res, hipStream_t st,
-                               hipEvent_t* ev, uint32_t ftab, uint32_t skip, uint32_t strands, DevCtx* ctx)
+                               hipEvent_t* ev, const TableWants& want, uint32_t strands, DevCtx* ctx)
 {
   if (dq->device != di->device || dq->K != di->K) return KFMI_E_BAD_ARGUMENT;
   if (!dq->ascii && dq->K == 3) return KFMI_E_BAD_ARGUMENT;
@@ -296,9 +296,7 @@ static int32_t strands_enqueue(kfmi_dev_index* di, kfmi_dev_queries* dq, uint32_
   SearchLaunch a{};
   a.st = st;
   a.ix = idx_args(di);
-  int32_t err = use_ftab(di, st, a.ix, ftab);
-  if (!err) err = use_rtab(di, st, a.ix, dq->rem);
-  if (!err) err = use_skip(di, st, a.ix, skip);
+  int32_t err = use_tables(di, st, a.ix, want, dq->rem);
   if (err) return err;
   a.maxw = strand_fused_maxw(di, dq->ascii != nullptr, dq->K, dq->steps, dq->rem);
   if (!a.maxw) {
@@ -342,13 +340,11 @@ extern "C" int32_t kfmi_search_strands(void* index, void* queries, void* results
   if (!f->dev || !q->dev || !r->d_results) return KFMI_E_NOT_ON_DEVICE;
   kfmi_dev_index* di = f->dev;
   if (r->d_device != di->device) return KFMI_E_BAD_ARGUMENT;
-  DevCtx* ctx = nullptr;
-  int32_t err = ctx_for(di->device, &ctx);
-  hipEvent_t* ev = err ? nullptr : thread_events(di->device);
-  hipStream_t st = err ? nullptr : thread_stream(di->device);
-  if (!err && (!ev || !st)) err = KFMI_E_NO_DEVICE;
-  if (!err) err = strands_enqueue(di, q->dev, r->d_results, st, ev, ftab_bases(), skip_wanted(), strands, ctx);
-  if (!err) err = search_finish(st, ev, t_ms);
+  SearchLane l;
+  int32_t err = search_lane(di->device, &l);
+  const TableWants want = tables_wanted().no_jump();   /* a strand search never takes the text jump */
+  if (!err) err = strands_enqueue(di, q->dev, r->d_results, l.st, l.ev, want, strands, l.ctx);
+  if (!err) err = search_finish(l.st, l.ev, t_ms);
   return err;
 }
 

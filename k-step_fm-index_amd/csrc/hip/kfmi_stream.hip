@@ -344,7 +344,7 @@ extern "C" int32_t kfmi_stream_release(void)
  * slice of a device group).  ms3 = {wall, host packing/staging, blocked on
  * the GPU}; *npacked = reads sent as host-packed words. */
 static int32_t stream_on(kfmi_dev_index* di, int member, const char* ascii, uint64_t num, uint32_t size,
-                         uint32_t* results, uint64_t chunk, uint32_t ftab, uint32_t skip, double* ms3,
+                         uint32_t* results, uint64_t chunk, const TableWants& want, double* ms3,
                          uint64_t* npacked_out, uint32_t strands = KFMI_STRAND_FWD)
 {
   /* strands != FWD: ns intervals per read (task 2q + strand in BOTH); a chunk's
@@ -417,9 +417,7 @@ static int32_t stream_on(kfmi_dev_index* di, int member, const char* ascii, uint
   const auto t0 = std::chrono::steady_clock::now();
   const Op op = is_coop(di->backend) ? Op::Coop : Op::Task;
   IdxArgs ix = idx_args(di);
-  err = use_ftab(di, ctx->st, ix, ftab);   /* the caller's setting (member threads have their own) */
-  if (!err) err = use_rtab(di, ctx->st, ix, rem);   /* rem != 0: the table, no ftab (as kfmi_search) */
-  if (!err) err = use_skip(di, ctx->st, ix, skip);
+  err = use_tables(di, ctx->st, ix, want, rem);   /* the caller's settings: member threads have their own */
   if (err) return err;
   int32_t status = KFMI_SUCCESS;
   using clk = std::chrono::steady_clock;
@@ -563,9 +561,10 @@ extern "C" int32_t kfmi_search_stream_strands(void* index, const char* ascii, ui
   double ms[KFMI_MAX_GROUP][3] = {};
   uint64_t np[KFMI_MAX_GROUP] = {};
   int32_t err = KFMI_SUCCESS;
-  const uint32_t ftab = ftab_bases(), skip = strands == KFMI_STRAND_FWD ? tables_wanted() : skip_wanted();
+  /* the strand leg never takes the text jump */
+  const TableWants want = strands == KFMI_STRAND_FWD ? tables_wanted() : tables_wanted().no_jump();
   if (!g) {
-    err = stream_on(f->dev, 0, ascii, num, size, results, chunk, ftab, skip, ms[0], &np[0], strands);
+    err = stream_on(f->dev, 0, ascii, num, size, results, chunk, want, ms[0], &np[0], strands);
   } else {
     const int n = g->n;
     uint64_t per = (num + n - 1) / n;
@@ -576,8 +575,8 @@ extern "C" int32_t kfmi_search_stream_strands(void* index, const char* ascii, ui
     for (int i = 0; i < n; ++i) {
       const uint64_t a = per * i < num ? per * i : num, b = per * (i + 1) < num ? per * (i + 1) : num;
       th.emplace_back([&, i, a, b] {
-        errs[i] = stream_on(g->di[i], i, ascii + a * size, b - a, size, results + 2 * ns * a, chunk, ftab, skip,
-                            ms[i], &np[i], strands);
+        errs[i] = stream_on(g->di[i], i, ascii + a * size, b - a, size, results + 2 * ns * a, chunk, want, ms[i],
+                            &np[i], strands);
       });
     }
     for (auto& t : th) t.join();

@@ -217,16 +217,13 @@ extern "C" int32_t kfmi_verify_seeds(void* index, void* queries, void* intervals
   if (dq->device != di->device || dq->num != q->num || dq->size != q->size) return KFMI_E_BAD_ARGUMENT;
   if (ri->d_device != di->device || rs->d_device != di->device || rh->d_device != di->device)
     return KFMI_E_BAD_ARGUMENT;
-  DevCtx* ctx = nullptr;
-  int32_t err = ctx_for(di->device, &ctx);
-  hipEvent_t* ev = err ? nullptr : thread_events(di->device);
-  hipStream_t st = err ? nullptr : thread_stream(di->device);
-  if (!err && (!ev || !st)) err = KFMI_E_NO_DEVICE;
+  SearchLane l;
+  int32_t err = search_lane(di->device, &l);
   if (err) return err;
   /* the text jump's tables, built here where the copy has none -- the path
    * kfmi_set_jump(1) takes at a first search, whatever this thread's setting */
   IdxArgs ix = idx_args(di);
-  err = use_jump(di, st, ix, 1u);
+  err = use_jump(di, l.st, ix, 1u);
   if (err) return err;
   if (!ix.jsa) return KFMI_E_NOT_IMPLEMENTED;   /* the index failed the tables' exactness check */
   VerifyArgs a{};
@@ -243,11 +240,11 @@ extern "C" int32_t kfmi_verify_seeds(void* index, void* queries, void* intervals
   a.max_occ = max_occ;
   a.max_mism = max_mism;
   a.split4 = split_for(8ull * di->bwtsize, LAY_INTER) == 4u ? 1u : 0u;
-  HIP_OK(hipEventRecord(ev[0], st));
-  HIP_OK(hipEventRecord(ev[1], st));
-  if (dq->num) HIP_OK(launch_verify(a, st));
-  HIP_OK(hipEventRecord(ev[2], st));
-  err = search_finish(st, ev, t_ms);
+  HIP_OK(hipEventRecord(l.ev[0], l.st));
+  HIP_OK(hipEventRecord(l.ev[1], l.st));
+  if (dq->num) HIP_OK(launch_verify(a, l.st));
+  HIP_OK(hipEventRecord(l.ev[2], l.st));
+  err = search_finish(l.st, l.ev, t_ms);
   t_ms[0] = t_ms[2];   /* total, 0, the verify kernel: nothing is packed beforehand */
   t_ms[1] = 0.0;
   return err;

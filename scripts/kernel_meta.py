@@ -4,8 +4,11 @@ one JSON line per kernel with its demangled name, VGPRs, SGPRs, scratch and LDS
 bytes, kernarg bytes and code size.  With --against DIR it compares every
 kernel whose name matches --match with the same object under DIR (names are
 compared after removing the trace policy parameter) and exits 1 on a difference.
+With --by-name the comparison is by kernel name across all the objects, for a
+change that moves a kernel from one object to another.
 
   scripts/kernel_meta.py --match 'skip_walk|task_kernel' obj/hip_kfmi_inst_mid_k2.o --against ../parent/obj
+  scripts/kernel_meta.py --by-name obj/hip_*.o --against ../parent/obj
 """
 import argparse
 import json
@@ -22,7 +25,12 @@ LLVM = Path(os.environ.get("ROCM", "/opt/rocm")) / "llvm" / "bin"
 def kernels(obj: Path, arch: str):
     with tempfile.TemporaryDirectory() as tmp:
         fat, co = Path(tmp) / "dev.fatbin", Path(tmp) / "dev.co"
-        subprocess.run([str(LLVM / "llvm-objcopy"), f"--dump-section=.hip_fatbin={fat}", str(obj)], check=True)
+        cp = subprocess.run([str(LLVM / "llvm-objcopy"), f"--dump-section=.hip_fatbin={fat}", str(obj)],
+                            capture_output=True, text=True)
+        if cp.returncode and "section '.hip_fatbin' not found" in cp.stderr:
+            return []   # a host-only unit
+        if cp.returncode:
+            sys.exit(cp.stderr)
         subprocess.run([str(LLVM / "clang-offload-bundler"), "--type=o", "--unbundle", f"--input={fat}",
                         f"--output={co}", f"--targets=hipv4-amdgcn-amd-amdhsa--{arch}"], check=True)
         notes = subprocess.run([str(LLVM / "llvm-readelf"), "--notes", str(co)], check=True, capture_output=True,
@@ -55,13 +63,46 @@ def plain(name: str) -> str:
     return name.replace(", kfmi::NoTrace>", ">")
 
 
+FIELDS = ("vgpr", "sgpr", "scratch", "lds", "code", "kernarg")
+
+
+def by_name(objects, arch: str, match: str):
+    """name -> the sorted metadata rows of every kernel of that name in `objects`."""
+    out = {}
+    for obj in objects:
+        for r in kernels(obj, arch):
+            if re.search(match, r["name"]):
+                out.setdefault(plain(r["name"]), []).append(tuple(r[f] for f in FIELDS))
+    return {n: sorted(v) for n, v in out.items()}
+
+
+def compare_by_name(a) -> int:
+    """Every kernel of a.objects against the kernel of the same name in any
+    hip_*.o under a.against: a kernel may move to another object.  Prints one
+    summary line, then a line per kernel that differs or exists on one side."""
+    mine = by_name(a.objects, a.arch, a.match)
+    theirs = by_name(sorted(a.against.glob("hip_*.o")), a.arch, a.match)
+    diff = sorted(n for n in set(mine) | set(theirs) if mine.get(n) != theirs.get(n))
+    print(json.dumps({"kernels_here": sum(map(len, mine.values())), "kernels_there": sum(map(len, theirs.values())),
+                      "names": len(mine), "differing": len(diff), "fields": FIELDS}))
+    for n in diff:
+        print(json.dumps({"kernel": n, "here": mine.get(n), "there": theirs.get(n)}))
+    return len(diff)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("objects", nargs="+", type=Path)
     ap.add_argument("--arch", default="gfx950")
     ap.add_argument("--match", default=".")
     ap.add_argument("--against", type=Path)
+    ap.add_argument("--by-name", action="store_true",
+                    help="with --against: compare by kernel name across all objects, not object by object")
     a = ap.parse_args()
+    if a.by_name:
+        if not a.against:
+            ap.error("--by-name needs --against")
+        sys.exit(1 if compare_by_name(a) else 0)
     bad = 0
     for obj in a.objects:
         mine = {plain(r["name"]): r for r in kernels(obj, a.arch) if re.search(a.match, r["name"])}
