@@ -353,6 +353,49 @@ int32_t     kfmi_device_jump_lines(void *index, uint32_t member, uint32_t *out, 
  * its window, out[4] = the window's bit offset there, out[5] = the dwords the
  * compare reads. */
 int32_t     kfmi_jump_line_geometry(uint64_t n, uint64_t p, uint32_t nb, uint64_t *out);
+/* Folded jump-start table (not in the reference; DESIGN.md 5a''''): a read whose
+ * jump-start entry is the one row [L, L + 1) next loads SA[L] for its text
+ * jump, a value that depends on the index alone.  The auto table of an upload
+ * that also built the text jump's tables therefore carries it: with n = rows - 1,
+ * an entry {x, y} holds x = L and y = R - L, except that a one-row entry holds
+ * y = 0xFFFFFFFF - SA[L].  The y codes 0xFFFFFFFF - n .. 0xFFFFFFFF are
+ * positions, so the form is lossless exactly when every width other than 1 is
+ * below 0xFFFFFFFF - n (kfmi_ftab_fold_bound): always for n < 2^31, by the
+ * text above that.  The upload decides it with a pass over the table and
+ * leaves a table that does not fit as {L, R}; that is no error.  Every kernel
+ * that reads the table decodes the entry; only the text jump uses the position,
+ * and no result changes.  Tables built at a search (an explicit kfmi_set_ftab
+ * count, or an index uploaded under other settings) are never folded.  No
+ * device memory is added.
+ *   kfmi_set_ftab_fold / KFMI_FTAB_FOLD (process-wide, default 1; an upload
+ * reads it when it builds its tables): 0 keeps every table {L, R}.
+ * kfmi_set_ftab_fold_bound (test knob, process-wide): a value other than 0
+ * lowers the bound of the fit rule to it, so the "does not fit" branch runs on
+ * a small index; 0 = the rule's own bound. */
+int32_t     kfmi_set_ftab_fold(uint32_t on);
+uint32_t    kfmi_ftab_fold(void);
+int32_t     kfmi_set_ftab_fold_bound(uint32_t bound);
+/* Host arithmetic of the folded form, for the tests.  The fit rule's bound
+ * for an n-base text, and whether a table whose largest width other than 1 is
+ * max_width fits it. */
+uint32_t    kfmi_ftab_fold_bound(uint64_t n);
+uint32_t    kfmi_ftab_fold_fits(uint64_t n, uint64_t max_width);
+/* out[0 .. 1] = the folded entry {x, y} of [L, R) with p = SA[L] (read only
+ * when R = L + 1); KFMI_E_BAD_ARGUMENT when the width does not fit the rule or
+ * p > n. */
+int32_t     kfmi_ftab_fold_encode(uint64_t n, uint32_t L, uint32_t R, uint32_t p, uint32_t *out);
+/* out[0 .. 2] = L, R and p (0xFFFFFFFF when the entry carries none) of the
+ * entry {x, y} of a table that is folded (folded != 0) or not: the decode every
+ * kernel takes. */
+int32_t     kfmi_ftab_fold_decode(uint64_t n, uint32_t x, uint32_t y, uint32_t folded, uint32_t *out);
+/* Test accessor: `count` raw entries from entry `first` of the auto
+ * jump-start table of the single-device copy (member 0) or of member `member`
+ * of a device group, copied to out[2 * count] as stored; *bases and *folded
+ * (either may be null) = the table's base count and whether it is in the
+ * folded form.  KFMI_E_NOT_ON_DEVICE without an auto table, KFMI_E_BAD_ARGUMENT
+ * when the range leaves the table. */
+int32_t     kfmi_device_ftab_entries(void *index, uint32_t member, uint32_t *out, uint64_t first, uint64_t count,
+                                     uint32_t *bases, uint32_t *folded);
 /* Test knobs of the search path (not in the reference), process-wide; their
  * environment variables are read once, at the first search, and these setters
  * switch them afterwards.  Split class (KFMI_SPLIT): the fetch form the task
@@ -752,10 +795,14 @@ int32_t kfmi_results_to_device(void *results);
  *           BAD_ISA (the ISA entry is no row; never on a valid table); bits
  *           4-15 the K-step position `pos` at which it tried; bits 16-31 the
  *           bases left there, (steps - pos) * K;
- *   word 2  the K-steps the jump start covered: 0, or the table's step count;
+ *   word 2  bits 0-30 the K-steps the jump start covered: 0, or the table's
+ *           step count; bit 31 (KFMI_TRACE_START_FOLDED) the lane's jump used
+ *           the text position its jump-start entry carried (a folded table,
+ *           kfmi_set_ftab_fold), so it issued no SA load;
  *   word 3  IdxArgs::jump_split as the kernel received it, after the launch's
  *           read-length rule: bit 2 the gathers in four 16-lane groups, 0x100
- *           the line table in use, 0x200 its grouped form; 1 without the jump.
+ *           the line table in use, 0x200 its grouped form; 1 without the jump
+ *           (the kernel's own bit for a folded jump-start table is not stored).
  * Steps + 16 / K * matches + word 2 is the K-step count of the read, unless the
  * jump was TAKEN (then pos + bases left / K is).
  *   Only what the text jump serves has a traced kernel: one device, the
@@ -772,6 +819,7 @@ enum {
   KFMI_TRACE_JUMP_OUT_SHIFT = 2, KFMI_TRACE_JUMP_POS_SHIFT = 4, KFMI_TRACE_JUMP_NB_SHIFT = 16,
   KFMI_TRACE_JUMP_TAKEN = 0, KFMI_TRACE_JUMP_REFUSED = 1, KFMI_TRACE_JUMP_DIFFERED = 2, KFMI_TRACE_JUMP_BAD_ISA = 3
 };
+#define KFMI_TRACE_START_FOLDED 0x80000000u
 int32_t kfmi_search_trace(void *index, void *queries, void *results, uint32_t *trace);
 
 /* Diagnostic (not in the reference): replays the line requests a

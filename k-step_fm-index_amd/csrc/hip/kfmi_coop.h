@@ -236,9 +236,9 @@ __global__ __launch_bounds__(64 * CoopCfg<G>::WPB) void coop_kernel(IdxArgs ix, 
     uint32_t w0;
     if constexpr (MAXW > 0) w0 = cw[0];
     else w0 = qp[qs];
-    const uint2 lr = ix.ftab[w0 & ix.ftab_mask];
-    L = lr.x;
-    R = lr.y;
+    const FtabAt lr = ftab_lookup(ix, w0);
+    L = lr.L;
+    R = lr.R;
   }
   if (ix.rem) {   // wave-uniform: m % K != 0, the last rem bases from the remainder table
     if constexpr (MAXW == 0) rc = qp[(uint64_t) nwords * num + qs];

@@ -98,7 +98,10 @@ struct IdxArgs {
   uint32_t bwtsize;
   DollarArgs dl;
   // ftab (Bowtie-style jump start): [L, R) after the first ftab_steps K-steps,
-  // indexed by the low 2*K*ftab_steps bits of the query's code stream; null = off
+  // indexed by the low 2*K*ftab_steps bits of the query's code stream; null = off.
+  // A table may be in the folded form (DESIGN.md 5a'''', ftab_entry_at below):
+  // bit JUMP_FTAB_FOLDED of jump_split says so, and every reader decodes its
+  // entry through ftab_entry_at.
   const uint2* __restrict__ ftab;
   uint32_t ftab_steps, ftab_mask;
   // LAY_MIDAC: AltCounters counters of entries E-1, E (sentinel), E+1 (zero),
@@ -165,6 +168,10 @@ constexpr uint32_t JUMP_LINE_S = 16, JUMP_LINE_W = 256 - JUMP_LINE_S, JUMP_LINE_
 static_assert(JUMP_LINE_S == 16 && JUMP_LINE_S + 256 / 16 == JUMP_LINE_DW, "a line: S entries, then 256 bases in 16 dwords");
 // IdxArgs::jump_split
 constexpr uint32_t JUMP_SPLIT4 = 4u, JUMP_LINES = 0x100u, JUMP_LINES_GROUPED = 0x200u;
+// ix.ftab is in the folded form (use_ftab): a property of the table, carried
+// here because the bits of jump_split cost no scalar register; not part of
+// what the traced kernel stores as word 3 of a record
+constexpr uint32_t JUMP_FTAB_FOLDED = 0x400u;
 // Longest read whose launch takes the lines in the grouped form: four groups
 // of up to 17 loads cost more issue slots than the saved line is worth from
 // about 196 bases on (3 Gbase: profiles/r12/jump_sweep_r12*.jsonl, the table
@@ -196,6 +203,35 @@ __host__ __device__ constexpr JumpLineAt jump_line_at(uint32_t n, uint32_t p, ui
   const uint64_t line = (uint64_t) j * JUMP_LINE_DW;
   return JumpLineAt{line + e % JUMP_LINE_S, line + JUMP_LINE_TEXT + (s >> 4), (s & 15u) * 2u,
                     ((s + nb + 15u) >> 4) - (s >> 4)};
+}
+
+// The folded form of a jump-start table (DESIGN.md 5a''''), n = rows - 1:
+//   x = L;  y = R - L for an entry whose width is not 1;
+//   y = 0xFFFFFFFF - p for the one-row entry [L, L + 1), p = sa[L], 0 <= p <= n.
+// The codes 0xFFFFFFFF - n .. 0xFFFFFFFF of y are positions, so the form is
+// lossless exactly when every width other than 1 is below ftab_fold_bound(n)
+// (always for n < 2^31; above that it depends on the text).  A table that does
+// not fit stays {L, R}.  Every reader of ix.ftab decodes through ftab_entry_at:
+// [L, R) and p, SKIP_NONE when the entry carries no position.
+struct FtabAt {
+  uint32_t L, R, p;
+};
+__host__ __device__ constexpr uint32_t ftab_fold_bound(uint32_t n) { return 0xFFFFFFFFu - n; }
+__host__ __device__ constexpr bool ftab_fold_fits(uint32_t n, uint32_t max_width) { return max_width < ftab_fold_bound(n); }
+__host__ __device__ inline uint2 ftab_fold_entry(uint32_t L, uint32_t R, uint32_t p)
+{
+  return make_uint2(L, R - L == 1u ? 0xFFFFFFFFu - p : R - L);
+}
+__host__ __device__ inline FtabAt ftab_entry_at(uint2 e, bool folded, uint32_t n)
+{
+  if (!folded) return FtabAt{e.x, e.y, SKIP_NONE};
+  const uint32_t c = 0xFFFFFFFFu - e.y;   /* the position, when y holds one */
+  return c <= n ? FtabAt{e.x, e.x + 1u, c} : FtabAt{e.x, e.x + e.y, SKIP_NONE};
+}
+/* the decode of ix.ftab's entry for code stream word w0 */
+__device__ __forceinline__ FtabAt ftab_lookup(const IdxArgs& ix, uint32_t w0)
+{
+  return ftab_entry_at(ix.ftab[w0 & ix.ftab_mask], (ix.jump_split & JUMP_FTAB_FOLDED) != 0u, ix.bwtsize - 1u);
 }
 
 typedef unsigned int v4u __attribute__((ext_vector_type(4)));

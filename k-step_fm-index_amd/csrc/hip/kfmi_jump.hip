@@ -310,9 +310,10 @@ int32_t auto_jump(kfmi_dev_index* di, hipStream_t st)
  * they are not there (an index that fails the exactness check still has none). */
 int32_t use_jump(kfmi_dev_index* di, hipStream_t st, IdxArgs& ix, uint32_t want)
 {
+  const uint32_t folded = ix.jump_split & JUMP_FTAB_FOLDED;   /* use_ftab's bit: the table's, not the jump's */
   ix.jsa = nullptr;
   ix.jump_min = 0xFFFFFFFFu;
-  ix.jump_split = 1;
+  ix.jump_split = 1 | folded;
   if (!want || !jump_applies(di)) return KFMI_SUCCESS;
   if (want == 2) {
     const int32_t e = auto_jump(di, st);
@@ -331,7 +332,8 @@ int32_t use_jump(kfmi_dev_index* di, hipStream_t st, IdxArgs& ix, uint32_t want)
   ix.jump_min = g_jump_min.load(std::memory_order_relaxed);
   const uint32_t lines = kfmi_jump_lines();
   const bool split4 = split_for(8ull * di->bwtsize, LAY_INTER) == 4u;
-  ix.jump_split = (split4 ? JUMP_SPLIT4 : 0u) | (lines ? JUMP_LINES : 0u) | (lines == 1u && split4 ? JUMP_LINES_GROUPED : 0u);
+  ix.jump_split = (split4 ? JUMP_SPLIT4 : 0u) | (lines ? JUMP_LINES : 0u) | (lines == 1u && split4 ? JUMP_LINES_GROUPED : 0u) |
+                  folded;
   return KFMI_SUCCESS;
 }
 

@@ -247,7 +247,9 @@ struct Trace {
  * choice of addresses for the same loads, the same wait and the same compare.
  * A lane whose compare fails keeps the state it had, never jumps again and goes
  * on through the skip lookups and K-steps, so it returns the very empty
- * interval the walk returns.
+ * interval the walk returns.  A lane whose jump-start entry carried sa[L] (p0,
+ * a folded table: DESIGN.md 5a'''') takes that value in its first round and
+ * issues no jsa[L] load; everything after is the same.
  *   TR (kstep_fmi.h kfmi_search_trace): with Trace the same
  * body counts what the lane does -- K-steps, skip lookups that matched and that
  * did not, its one text jump -- and stores one 16-byte record when it leaves
@@ -255,11 +257,12 @@ struct Trace {
  * default, none of them is instantiated and `tr` is an empty object. */
 template <class G, int MAXW, int SPLIT, bool JUMP = false, class TR = NoTrace>
 __device__ __forceinline__ void skip_walk(const IdxArgs& ix, const uint32_t (&cw)[MAXW], uint32_t steps, uint32_t pos,
-                                          uint32_t& Lq, uint32_t& Rq, typename TR::Out tr = typename TR::Out{})
+                                          uint32_t& Lq, uint32_t& Rq, typename TR::Out tr = typename TR::Out{},
+                                          uint32_t p0 = SKIP_NONE)
 {
   static_assert(G::K <= 2 && MAXW > 0, "skip table: fused task kernels at K <= 2");
   /* TR: the record's words 0 .. 2 (kstep_fmi.h); the start is `pos` as the caller passed it */
-  [[maybe_unused]] uint32_t tr_walk = 0, tr_jump = 0, tr_line = 0;
+  [[maybe_unused]] uint32_t tr_walk = 0, tr_jump = 0, tr_line = 0, tr_fold = 0;
   [[maybe_unused]] const uint32_t tr_start = pos;
   extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
   const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
@@ -289,13 +292,21 @@ __device__ __forceinline__ void skip_walk(const IdxArgs& ix, const uint32_t (&cw
     uint32_t p = SKIP_NONE;
     if constexpr (JUMP) {
       jmp = row1 && !(fl & 2u) && L[0] < ix.bwtsize && (steps - pos) * (uint32_t) G::K >= ix.jump_min;
+      /* p0: sa[L] from the lane's jump-start entry (a folded table, DESIGN.md
+       * 5a''''), for its first round only -- then no jsa[L] load goes out */
+      const bool ld = jmp && p0 == SKIP_NONE;
       if (ix.jump_split & JUMP_SPLIT4) {   /* wave-uniform */
 #pragma unroll
         for (int g = 0; g < 4; ++g)
-          if (jmp && grp == g) p = ix.jsa[L[0]];
-      } else if (jmp) {
+          if (ld && grp == g) p = ix.jsa[L[0]];
+      } else if (ld) {
         p = ix.jsa[L[0]];
       }
+      if (jmp && !ld) {
+        p = p0;
+        if constexpr (TR::ON) tr_fold = KFMI_TRACE_START_FOLDED;
+      }
+      p0 = SKIP_NONE;
     }
     const bool one = row1 && !jmp && !is_dead() && L[0] < ix.skip_rows && pos + J <= steps;
     uint2 e = make_uint2(SKIP_NONE, 0u);
@@ -418,7 +429,7 @@ __device__ __forceinline__ void skip_walk(const IdxArgs& ix, const uint32_t (&cw
   }
   Lq = L[0];
   Rq = R[0];
-  if constexpr (TR::ON) *tr = make_uint4(tr_walk, tr_jump, tr_start, ix.jump_split);
+  if constexpr (TR::ON) *tr = make_uint4(tr_walk, tr_jump, tr_start | tr_fold, ix.jump_split & ~JUMP_FTAB_FOLDED);
 }
 
 /* The walk of a seed search (kfmi_seeds.hip, kstep_fmi.h section 2, DESIGN.md
@@ -522,9 +533,10 @@ __device__ __forceinline__ void seed_walk(const IdxArgs& ix, const uint32_t (&cw
         dead = true;
       }
     } else if (jump) {
-      if (te.y > te.x) {
-        L[0] = te.x;
-        R[0] = te.y;
+      const FtabAt fe = ftab_entry_at(te, (ix.jump_split & JUMP_FTAB_FOLDED) != 0u, ix.bwtsize - 1u);
+      if (fe.R > fe.L) {
+        L[0] = fe.L;
+        R[0] = fe.R;
         pos += F;
       } else {
         dead = true;
@@ -585,6 +597,7 @@ __global__ __launch_bounds__(256) void task_kernel(IdxArgs ix, const uint32_t* _
     R[i] = ix.bwtsize;
   }
   uint32_t skip = 0;
+  [[maybe_unused]] uint32_t p0 = SKIP_NONE;
   if (ix.ftab && steps >= ix.ftab_steps) {   /* wave-uniform: jump start from the ftab */
     skip = ix.ftab_steps;
 #pragma unroll
@@ -592,9 +605,10 @@ __global__ __launch_bounds__(256) void task_kernel(IdxArgs ix, const uint32_t* _
       uint32_t w0;
       if constexpr (MAXW > 0) w0 = cw[i][0];
       else w0 = qp[q[i]];
-      const uint2 lr = ix.ftab[w0 & ix.ftab_mask];
-      L[i] = lr.x;
-      R[i] = lr.y;
+      const FtabAt lr = ftab_lookup(ix, w0);
+      L[i] = lr.L;
+      R[i] = lr.R;
+      if constexpr (JUMP) p0 = lr.p;   /* sa[L] of a one-row entry of a folded table */
     }
   }
   if (ix.rem) {   /* wave-uniform: m % K != 0, the last rem bases from the remainder table */
@@ -604,9 +618,10 @@ __global__ __launch_bounds__(256) void task_kernel(IdxArgs ix, const uint32_t* _
       L[i] = lr.x;
       R[i] = lr.y;
     }
+    p0 = SKIP_NONE;   /* no jump start beside the remainder table (use_rtab) */
   }
   if constexpr (SKIP) {
-    skip_walk<G, MAXW, SPLIT, JUMP, TR>(ix, cw[0], steps, skip, L[0], R[0], TR::at(trace, base));
+    skip_walk<G, MAXW, SPLIT, JUMP, TR>(ix, cw[0], steps, skip, L[0], R[0], TR::at(trace, base), p0);
     *reinterpret_cast<uint2*>(res + 2 * base) = make_uint2(L[0], R[0]);
     return;
   }
@@ -678,9 +693,9 @@ __global__ __launch_bounds__(256) void task_words_skip_kernel(IdxArgs ix, const 
   uint32_t L = 0, R = ix.bwtsize, skip = 0;
   if (ix.ftab && steps >= ix.ftab_steps) {   /* wave-uniform: jump start from the ftab */
     skip = ix.ftab_steps;
-    const uint2 lr = ix.ftab[cw[0] & ix.ftab_mask];
-    L = lr.x;
-    R = lr.y;
+    const FtabAt lr = ftab_lookup(ix, cw[0]);
+    L = lr.L;
+    R = lr.R;
   }
   if (ix.rem) {   /* wave-uniform: m % K != 0, the last rem bases from the remainder table */
     const uint2 lr = ix.rtab[qp[(uint64_t) nwords * num + q]];
@@ -750,9 +765,9 @@ __global__ __launch_bounds__(256) void task_strands_kernel(IdxArgs ix, const uin
   uint32_t L = 0, R = ix.bwtsize, skip = 0;
   if (ix.ftab && steps >= ix.ftab_steps) {   /* wave-uniform: jump start from the ftab */
     skip = ix.ftab_steps;
-    const uint2 lr = ix.ftab[cw[0] & ix.ftab_mask];
-    L = lr.x;
-    R = lr.y;
+    const FtabAt lr = ftab_lookup(ix, cw[0]);
+    L = lr.L;
+    R = lr.R;
   }
   skip_walk<G, MAXW, SPLIT>(ix, cw, steps, skip, L, R);
   *reinterpret_cast<uint2*>(res + 2 * t) = make_uint2(L, R);

@@ -57,6 +57,10 @@ struct kfmi_dev_index {
   /* bases of the auto table (KFMI_FTAB_AUTO), decided once per device copy
    * under ftab_mu (auto_ftab): -1 not yet, 0 none */
   int ftab_auto = -1;
+  /* bit N: ftab[N] is in the folded form (kfmi_device.h ftab_entry_at): set by
+   * an upload's fold pass (auto_tables) for its auto table alone, under the
+   * handle's exclusive lock; cleared with the table */
+  uint32_t ftab_folded = 0;
   /* skip table (DESIGN.md 5a'): one {row, code} entry per BWT row, K <= 2, task
    * backends; same lifetime rule and mutex as the ftabs.  skip_auto: the auto
    * decision of this copy (auto_skip): -1 not yet, 0 none, 1 built */

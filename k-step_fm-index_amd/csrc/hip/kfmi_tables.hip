@@ -184,6 +184,7 @@ static int32_t use_rtab(kfmi_dev_index* di, hipStream_t st, IdxArgs& ix, uint32_
   ix.ftab = nullptr;
   ix.ftab_steps = 0;
   ix.ftab_mask = 0;
+  ix.jump_split &= ~JUMP_FTAB_FOLDED;
   return KFMI_SUCCESS;
 }
 
@@ -217,16 +218,20 @@ static int32_t build_ftab(kfmi_dev_index* di, hipStream_t st, uint32_t bases)
  * fewer until one can or none is left.  Never an allocation error: the search
  * then walks every step.  Called from the uploads (auto_tables) and, for an
  * index uploaded under another setting, from use_ftab.  *bases (may be null) =
- * its base count, 0 when it has none. */
-static int32_t auto_ftab(kfmi_dev_index* di, hipStream_t st, uint32_t* bases)
+ * its base count, 0 when it has none; *built (may be null) = this call built it. */
+static int32_t auto_ftab(kfmi_dev_index* di, hipStream_t st, uint32_t* bases, bool* built = nullptr)
 {
   std::lock_guard<std::mutex> lk(di->ftab_mu);
+  if (built) *built = false;
   if (di->ftab_auto < 0) {
     uint32_t n = kfmi_ftab_auto_bases(di->bwtsize, di->K, table_budget_now());
     for (; n; n -= di->K) {
       if (di->ftab[n]) break;   /* an explicit setting built it already */
       const int32_t e = build_ftab(di, st, n);
-      if (!e) break;
+      if (!e) {
+        if (built) *built = true;
+        break;
+      }
       if (e != KFMI_E_DEVICE_ALLOC) return e;
     }
     di->ftab_auto = (int) n;
@@ -244,6 +249,7 @@ static int32_t use_ftab(kfmi_dev_index* di, hipStream_t st, IdxArgs& ix, uint32_
   ix.ftab = nullptr;
   ix.ftab_steps = 0;
   ix.ftab_mask = 0;
+  ix.jump_split &= ~JUMP_FTAB_FOLDED;
   if (bases == KFMI_FTAB_AUTO) {
     const int32_t e = auto_ftab(di, st, &bases);
     if (e) return e;
@@ -255,6 +261,7 @@ static int32_t use_ftab(kfmi_dev_index* di, hipStream_t st, IdxArgs& ix, uint32_
       const int32_t e = build_ftab(di, st, bases);
       if (e) return e;
     }
+    if ((di->ftab_folded >> bases) & 1u) ix.jump_split |= JUMP_FTAB_FOLDED;   /* the table's form goes with its pointer */
   }
   ix.ftab = di->ftab[bases];
   ix.ftab_steps = bases / di->K;
@@ -381,6 +388,145 @@ static int32_t use_skip(kfmi_dev_index* di, hipStream_t st, IdxArgs& ix, uint32_
   return KFMI_SUCCESS;
 }
 
+/* ---- folded jump-start table (DESIGN.md 5a'''', kfmi_device.h ftab_entry_at) ---- */
+static std::atomic<int> g_ftab_fold{-1};          /* -1: KFMI_FTAB_FOLD, else 1; kfmi_set_ftab_fold */
+static std::atomic<uint32_t> g_ftab_fold_bound{0};   /* test knob: lowers the fit rule's bound; 0 = the rule's own */
+
+extern "C" int32_t kfmi_set_ftab_fold(uint32_t on)
+{
+  if (on > 1) return KFMI_E_BAD_ARGUMENT;
+  g_ftab_fold.store((int) on, std::memory_order_relaxed);
+  return KFMI_SUCCESS;
+}
+
+extern "C" uint32_t kfmi_ftab_fold(void)
+{
+  const int v = g_ftab_fold.load(std::memory_order_relaxed);
+  if (v >= 0) return (uint32_t) v;
+  static const uint32_t env = [] {   /* KFMI_FTAB_FOLD, read once per process */
+    const char* e = getenv("KFMI_FTAB_FOLD");
+    return !e || !*e || atoi(e) ? 1u : 0u;
+  }();
+  return env;
+}
+
+extern "C" int32_t kfmi_set_ftab_fold_bound(uint32_t bound)
+{
+  g_ftab_fold_bound.store(bound, std::memory_order_relaxed);
+  return KFMI_SUCCESS;
+}
+
+/* The host's view of the folded form, for the tests (pure arithmetic). */
+extern "C" uint32_t kfmi_ftab_fold_bound(uint64_t n) { return n >= 0xFFFFFFFFull ? 0u : ftab_fold_bound((uint32_t) n); }
+
+extern "C" uint32_t kfmi_ftab_fold_fits(uint64_t n, uint64_t max_width)
+{
+  return n < 0xFFFFFFFFull && max_width <= 0xFFFFFFFFull && ftab_fold_fits((uint32_t) n, (uint32_t) max_width) ? 1u : 0u;
+}
+
+extern "C" int32_t kfmi_ftab_fold_encode(uint64_t n, uint32_t L, uint32_t R, uint32_t p, uint32_t* out)
+{
+  if (!out || n >= 0xFFFFFFFFull) return KFMI_E_BAD_ARGUMENT;
+  if (R - L == 1u ? (uint64_t) p > n : !ftab_fold_fits((uint32_t) n, R - L)) return KFMI_E_BAD_ARGUMENT;
+  const uint2 e = ftab_fold_entry(L, R, p);
+  out[0] = e.x;
+  out[1] = e.y;
+  return KFMI_SUCCESS;
+}
+
+extern "C" int32_t kfmi_ftab_fold_decode(uint64_t n, uint32_t x, uint32_t y, uint32_t folded, uint32_t* out)
+{
+  if (!out || n >= 0xFFFFFFFFull) return KFMI_E_BAD_ARGUMENT;
+  const FtabAt at = ftab_entry_at(make_uint2(x, y), folded != 0u, (uint32_t) n);
+  out[0] = at.L;
+  out[1] = at.R;
+  out[2] = at.p;
+  return KFMI_SUCCESS;
+}
+
+/* The fit rule's input: the largest width other than 1 of the table's entries,
+ * 0xFFFFFFFF when a one-row entry names no row of the index (never on a valid
+ * table; it refuses the fold).  Streaming; one atomic per wave. */
+__global__ __launch_bounds__(256) void ftab_fold_check_kernel(const uint2* __restrict__ t, uint64_t entries, uint32_t rows,
+                                                              uint32_t* __restrict__ maxw)
+{
+  uint32_t m = 0;
+  for (uint64_t i = (uint64_t) blockIdx.x * 256 + threadIdx.x; i < entries; i += (uint64_t) gridDim.x * 256) {
+    const uint2 e = t[i];
+    const uint32_t w = e.y - e.x;
+    if (w != 1u) m = max(m, w);
+    else if (e.x >= rows) m = 0xFFFFFFFFu;
+  }
+#pragma unroll
+  for (int o = 32; o; o >>= 1) m = max(m, (uint32_t) __shfl_xor((int) m, o));
+  if ((threadIdx.x & 63u) == 0u && m) atomicMax(maxw, m);
+}
+
+/* {L, R} -> the folded entry, in place, every thread its own entries.  The
+ * sa[L] gather of the one-row entries goes out as four exec-masked 16-lane
+ * groups where sa lies past the translation reach (`split`, split_for), as the
+ * other gathers into the text jump's tables do.  L < rows (the check above). */
+__global__ __launch_bounds__(256) void ftab_fold_kernel(uint2* __restrict__ t, uint64_t entries,
+                                                        const uint32_t* __restrict__ sa, uint32_t split)
+{
+  const int grp = (int) (threadIdx.x & 63) / 16;
+  for (uint64_t i0 = (uint64_t) blockIdx.x * 256 + (threadIdx.x & ~63u); i0 < entries; i0 += (uint64_t) gridDim.x * 256) {
+    const uint64_t i = i0 + (threadIdx.x & 63u);
+    const bool on = i < entries;
+    const uint2 e = on ? t[i] : make_uint2(0u, 0u);
+    const bool one = on && e.y - e.x == 1u;
+    uint32_t p = 0u;
+    if (split) {   /* wave-uniform */
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+        if (one && grp == g) p = sa[e.x];
+    } else if (one) {
+      p = sa[e.x];
+    }
+    if (on) t[i] = ftab_fold_entry(e.x, e.y, p);
+  }
+}
+
+/* The fold pass of an upload (auto_tables; the handle is locked exclusively, so
+ * nothing reads the copy): the auto table this upload built, rewritten into the
+ * folded form when the fit rule holds for it -- decided on the device by a
+ * reduction over the table -- and left {L, R} otherwise, which is no error.
+ * The text jump's tables are this upload's own, so their exactness check passed
+ * and every sa value is a position <= n. */
+static int32_t fold_ftab(kfmi_dev_index* di, hipStream_t st)
+{
+  if (!kfmi_ftab_fold()) return KFMI_SUCCESS;
+  std::lock_guard<std::mutex> lk(di->ftab_mu);
+  const int N = di->ftab_auto;
+  if (N <= 0 || !di->ftab[N] || !di->jump_sa || ((di->ftab_folded >> N) & 1u)) return KFMI_SUCCESS;
+  const uint64_t entries = 1ull << (2 * N);
+  const uint32_t rows = di->bwtsize;
+  uint32_t* d_max = nullptr;
+  if (hipMalloc((void**) &d_max, 4) != hipSuccess) {
+    (void) hipGetLastError();
+    return KFMI_SUCCESS;
+  }
+  uint32_t h_max = 0xFFFFFFFFu;
+  const dim3 grid(grid_blocks((entries + 255) / 256, 1u << 14));
+  bool ok = hipMemsetAsync(d_max, 0, 4, st) == hipSuccess;
+  if (ok) {
+    hipLaunchKernelGGL(ftab_fold_check_kernel, grid, dim3(256), 0, st, di->ftab[N], entries, rows, d_max);
+    ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(&h_max, d_max, 4, hipMemcpyDeviceToHost, st) == hipSuccess &&
+         hipStreamSynchronize(st) == hipSuccess;
+  }
+  (void) hipFree(d_max);
+  if (!ok) return KFMI_E_KERNEL;
+  uint32_t bound = ftab_fold_bound(rows - 1u);
+  const uint32_t lowered = g_ftab_fold_bound.load(std::memory_order_relaxed);
+  if (lowered && lowered < bound) bound = lowered;
+  if (h_max >= bound) return KFMI_SUCCESS;   /* does not fit: the table stays {L, R} */
+  const uint32_t split = split_for(8ull * rows, LAY_INTER) == 4u ? 1u : 0u;
+  hipLaunchKernelGGL(ftab_fold_kernel, grid, dim3(256), 0, st, di->ftab[N], entries, di->jump_sa, split);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return KFMI_E_KERNEL;
+  di->ftab_folded |= 1u << N;
+  return KFMI_SUCCESS;
+}
+
 /* ---- one call per search, one per upload ---- */
 /* The tables of one search under the caller's settings `w`, set in ix, each
  * built first where `w` asks for it and the copy has none: the ftab, the
@@ -399,13 +545,22 @@ int32_t use_tables(kfmi_dev_index* di, hipStream_t st, IdxArgs& ix, const TableW
 
 /* An upload's part, like the re-layout, so that no search pays for a build:
  * each table whose resolved setting is auto, decided and built once (device
- * `di->device` current): ftab, skip, jump.  Not fitting is never an error. */
+ * `di->device` current): ftab, skip, jump.  Not fitting is never an error.
+ * Last, the fold pass (fold_ftab) -- here only: a table built at a search, while
+ * other searches may hold the shared lock, is never rewritten. */
 int32_t auto_tables(kfmi_dev_index* di, hipStream_t st, const TableWants& w)
 {
   int32_t err = KFMI_SUCCESS;
-  if (w.ftab == KFMI_FTAB_AUTO) err = auto_ftab(di, st, nullptr);
+  bool ftab_built = false, jump_built = false;
+  if (w.ftab == KFMI_FTAB_AUTO) err = auto_ftab(di, st, nullptr, &ftab_built);
   if (!err && w.skip == 2u) err = auto_skip(di, st);
-  if (!err && w.jump == 2u) err = auto_jump(di, st);
+  if (!err && w.jump == 2u) {
+    const bool had = di->jump_sa != nullptr;
+    err = auto_jump(di, st);
+    jump_built = !err && !had && di->jump_sa != nullptr;
+  }
+  /* the fold: only a table and text-jump tables this upload built itself */
+  if (!err && ftab_built && jump_built) err = fold_ftab(di, st);
   return err;
 }
 
@@ -427,6 +582,7 @@ void drop_ftabs(kfmi_dev_index* di)
       t = nullptr;
     }
   di->ftab_auto = -1;
+  di->ftab_folded = 0;
   if (di->skip) (void) hipFree(di->skip);   /* the skip table goes with them */
   di->skip = nullptr;
   di->skip_auto = -1;
@@ -479,6 +635,30 @@ static uint64_t skip_bytes_of(kfmi_dev_index* di)
 extern "C" uint64_t kfmi_device_ftab_bytes(void* index) { return sum_members(index, ftab_bytes_of); }
 
 extern "C" uint64_t kfmi_device_skip_bytes(void* index) { return sum_members(index, skip_bytes_of); }
+
+/* Test accessor: raw entries [first, first + count) of the auto jump-start table
+ * of the single-device copy or of a group member, as stored (kstep_fmi.h). */
+extern "C" int32_t kfmi_device_ftab_entries(void* index, uint32_t member, uint32_t* out, uint64_t first, uint64_t count,
+                                            uint32_t* bases, uint32_t* folded)
+{
+  kfmi_fmi_t* f = (kfmi_fmi_t*) index;
+  if (!f || !out) return KFMI_E_BAD_ARGUMENT;
+  DeviceGuard dg;
+  std::shared_lock<RwLock> lk(index_lock(f));
+  kfmi_dev_index* di = nullptr;
+  const int32_t e = member_index(f, member, &di);
+  if (e) return e;
+  std::lock_guard<std::mutex> tl(di->ftab_mu);
+  const int N = di->ftab_auto;
+  if (N <= 0 || !di->ftab[N]) return KFMI_E_NOT_ON_DEVICE;
+  const uint64_t entries = 1ull << (2 * N);
+  if (first > entries || count > entries - first) return KFMI_E_BAD_ARGUMENT;
+  if (hipSetDevice(di->device) != hipSuccess) return KFMI_E_NO_DEVICE;
+  if (count) HIP_OK(hipMemcpy(out, di->ftab[N] + first, 8ull * count, hipMemcpyDeviceToHost));
+  if (bases) *bases = (uint32_t) N;
+  if (folded) *folded = (di->ftab_folded >> N) & 1u;
+  return KFMI_SUCCESS;
+}
 
 /* Test accessor: the single-device copy's skip table copied to `out`
  * (`entries` uint2 {row, code}); KFMI_E_NOT_ON_DEVICE without a table or on a

@@ -138,6 +138,14 @@ def load() -> ctypes.CDLL:
         "kfmi_device_jump_line_bytes": (u64, [vp]),
         "kfmi_device_jump_lines": (i32, [vp, u32, vp, u64]),
         "kfmi_jump_line_geometry": (i32, [u64, u64, u32, ctypes.POINTER(ctypes.c_uint64)]),
+        "kfmi_set_ftab_fold": (i32, [u32]),
+        "kfmi_ftab_fold": (u32, []),
+        "kfmi_set_ftab_fold_bound": (i32, [u32]),
+        "kfmi_ftab_fold_bound": (u32, [u64]),
+        "kfmi_ftab_fold_fits": (u32, [u64, u64]),
+        "kfmi_ftab_fold_encode": (i32, [u64, u32, u32, u32, ctypes.POINTER(u32)]),
+        "kfmi_ftab_fold_decode": (i32, [u64, u32, u32, u32, ctypes.POINTER(u32)]),
+        "kfmi_device_ftab_entries": (i32, [vp, u32, vp, u64, u64, ctypes.POINTER(u32), ctypes.POINTER(u32)]),
         "kfmi_set_fused": (i32, [i32]),
         "kfmi_set_walk_check": (i32, [u32]),
         "kfmi_fail_index_uploads": (i32, [u32]),
@@ -210,6 +218,48 @@ def set_ftab_budget(nbytes) -> None:
     """Byte budget of the auto rule (process-wide test knob); None = a quarter
     of the free device memory."""
     _check(load().kfmi_set_ftab_budget(0xFFFFFFFFFFFFFFFF if nbytes is None else int(nbytes)), "set_ftab_budget")
+
+
+def set_ftab_fold(on) -> None:
+    """Folded jump-start table (kstep_fmi.h): 1 (the default) = an upload that
+    builds the auto table and the text jump's tables stores sa[L] in its
+    one-row entries; 0 = every table stays {L, R}.  Process-wide
+    (KFMI_FTAB_FOLD), read by an upload.  No setting changes a result."""
+    _check(load().kfmi_set_ftab_fold(int(on)), f"set_ftab_fold({on})")
+
+
+def ftab_fold() -> int:
+    return int(load().kfmi_ftab_fold())
+
+
+def set_ftab_fold_bound(bound) -> None:
+    """Test knob: lowers the bound of the fold's fit rule (None or 0 = the
+    rule's own, 0xFFFFFFFF - n), so a small index takes the "does not fit" branch."""
+    _check(load().kfmi_set_ftab_fold_bound(0 if bound is None else int(bound)), f"set_ftab_fold_bound({bound})")
+
+
+def ftab_fold_bound(n: int) -> int:
+    """The fit rule: a table of an n-base text folds when every width other than 1 is below this."""
+    return int(load().kfmi_ftab_fold_bound(int(n)))
+
+
+def ftab_fold_fits(n: int, max_width: int) -> bool:
+    return bool(load().kfmi_ftab_fold_fits(int(n), int(max_width)))
+
+
+def ftab_fold_encode(n: int, L: int, R: int, p: int = 0):
+    """The folded entry (x, y) of [L, R), p = sa[L] of a one-row entry; raises
+    KfmiError when the width does not fit the rule or p > n."""
+    out = (ctypes.c_uint32 * 2)()
+    _check(load().kfmi_ftab_fold_encode(int(n), int(L), int(R), int(p), out), f"ftab_fold_encode({n}, {L}, {R}, {p})")
+    return int(out[0]), int(out[1])
+
+
+def ftab_fold_decode(n: int, x: int, y: int, folded: bool = True):
+    """(L, R, p) of the entry (x, y) as every kernel decodes it; p = None when it carries no position."""
+    out = (ctypes.c_uint32 * 3)()
+    _check(load().kfmi_ftab_fold_decode(int(n), int(x), int(y), int(bool(folded)), out), "ftab_fold_decode")
+    return int(out[0]), int(out[1]), (None if int(out[2]) == 0xFFFFFFFF else int(out[2]))
 
 
 SKIP_AUTO = 0xFFFFFFFF
@@ -524,6 +574,22 @@ class Index(_Handle):
         _check(load().kfmi_device_jump_lines(self._p, int(member), out.ctypes.data_as(ctypes.c_void_p), lines),
                "jump_lines")
         return out
+
+    def ftab_entries(self, first: int = 0, count=None, member: int = 0):
+        """Test accessor: (bases, folded, uint32 [count, 2]) -- raw entries of the
+        auto jump-start table of the single-device copy or of a group member,
+        as stored: {L, R}, or the folded form when `folded`."""
+        L = load()
+        b, fo = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        if count is None:
+            probe = np.empty((0, 2), dtype=np.uint32)
+            _check(L.kfmi_device_ftab_entries(self._p, int(member), probe.ctypes.data_as(ctypes.c_void_p), 0, 0,
+                                              ctypes.byref(b), ctypes.byref(fo)), "ftab_entries")
+            count = (1 << (2 * int(b.value))) - int(first)
+        out = np.empty((int(count), 2), dtype=np.uint32)
+        _check(L.kfmi_device_ftab_entries(self._p, int(member), out.ctypes.data_as(ctypes.c_void_p), int(first),
+                                          int(count), ctypes.byref(b), ctypes.byref(fo)), "ftab_entries")
+        return int(b.value), bool(fo.value), out
 
     def skip_table(self):
         """Test accessor: (J, uint32 [rows, 2] of {row, code}) of the single-device copy's skip table."""
@@ -882,9 +948,17 @@ def decode_trace(records: np.ndarray) -> dict:
         "jump_nb": np.where(no, -1, (r[:, 1] >> 16) & 0xFFFF),
         "jump_line": np.where(no, -1, (r[:, 1] >> 1) & 1),
         "jump_outcome": np.where(no, -1, (r[:, 1] >> 2) & 3),
-        "start_steps": r[:, 2],
+        "start_steps": r[:, 2] & 0x7FFFFFFF,
         "jump_split": r[:, 3],
     }
+
+
+def trace_start_folded(records: np.ndarray) -> np.ndarray:
+    """Bit 31 of word 2 of kfmi_search_trace's records (KFMI_TRACE_START_FOLDED):
+    1 where the read's jump used the text position its jump-start entry carried
+    (a folded table), so no SA load was issued; int64 [N]."""
+    r = np.asarray(records, dtype=np.uint32).reshape(-1, 4).astype(np.int64)
+    return (r[:, 2] >> 31) & 1
 
 
 def search_trace(index: Index, reads: np.ndarray, backend: str | None = None):
