@@ -822,6 +822,63 @@ enum {
 #define KFMI_TRACE_START_FOLDED 0x80000000u
 int32_t kfmi_search_trace(void *index, void *queries, void *results, uint32_t *trace);
 
+/* The same for the strand and seed searches.  skip_walk inside the strand
+ * kernels and seed_walk take the jump-start and skip tables as shortcuts that
+ * check themselves too: a lookup that brings nothing, or never happens, leaves
+ * the lane on the ordinary K-steps, which end on the very intervals and records
+ * the lookup would have led to.  Both calls run the search their untraced
+ * counterpart would run on the same resident handles under the calling thread's
+ * settings -- the same tables, the same staging (fused or packed first), the
+ * same fetch form, through the same host code -- with the traced instantiation
+ * of the same kernel body, write their results as that call does, and copy one
+ * record of four words per task to the host array `trace`, in results order
+ * (task t at 4 * t; in BOTH t = 2q + strand).
+ *
+ * kfmi_search_strands_trace(index, queries, results, strands, trace): REV and
+ * BOTH only (FWD is kfmi_search_trace; here KFMI_E_BAD_ARGUMENT).  Words 0 and
+ * 2 are those of kfmi_search_trace; a strand search never takes the text jump,
+ * so word 1 is 0 and bit 31 of word 2 is never set; word 3 is the launch
+ * identity below.  A search that packs first while no skip table is in effect
+ * runs the plain walk of the packed words, which has no traced form:
+ * KFMI_E_NOT_IMPLEMENTED.
+ *
+ * kfmi_search_seeds_trace(index, queries, intervals, spans, max_seeds,
+ * strands, trace): kfmi_search_seeds, and per task
+ *   word 0  bits 0-15 the rounds in which the lane took an ordinary K-step --
+ *           the step that ends a segment counts, and so does the step on a unit
+ *           that does not occur on its own; bits 16-23 the skip lookups that
+ *           matched; bits 24-31 those that did not;
+ *   word 1  bits 0-15 the jump-start lookups whose decoded entry was not empty
+ *           (each covers the table's step count), bits 16-31 those whose entry
+ *           was empty;
+ *   word 2  bits 0-15 the units that did not occur on their own (the remainder
+ *           unit among them: its empty table entry costs no step); bits 16-23
+ *           the records stored, before the zero fill of the unused slots;
+ *   word 3  the launch identity.
+ *
+ * The launch identity (word 3 of both calls): bits 0-3 the fetch form of the
+ * kernel that ran (its SPLIT template value: 8, 7, 4 or 1); bits 4-7 its code
+ * registers / 8 (1 or 2); bits 8-11 the kernel, KFMI_TRACE_KERNEL_*; bits 12-15
+ * IdxArgs::skip_split as the kernel received it (1 without a skip table, else
+ * the table's size class; the gathers go out in four groups at 4); bit 16 the
+ * jump-start table in use is folded; bits 24-31 the jump-start table's step
+ * count, 0 without a table.
+ *
+ * Both refuse what has no traced kernel before anything runs or is written:
+ * KFMI_E_NOT_IMPLEMENTED for the coop and AltCounters backends, K = 3 / 4 and
+ * device-group handles, KFMI_E_BAD_ARGUMENT for a null `trace` and wherever the
+ * untraced call gives it.  For tests and diagnosis; not timed. */
+enum {
+  KFMI_SEED_TRACE_START_HIT = 1u, KFMI_SEED_TRACE_START_EMPTY = 1u << 16, KFMI_SEED_TRACE_RECORDS_SHIFT = 16,
+  KFMI_TRACE_ID_MAXW_SHIFT = 4, KFMI_TRACE_ID_KERNEL_SHIFT = 8, KFMI_TRACE_ID_SKIP_SPLIT_SHIFT = 12,
+  KFMI_TRACE_ID_FTAB_FOLDED = 1u << 16, KFMI_TRACE_ID_FTAB_STEPS_SHIFT = 24,
+  KFMI_TRACE_KERNEL_SEED = 0, KFMI_TRACE_KERNEL_SEED_STRANDS = 1, KFMI_TRACE_KERNEL_SEED_WORDS = 2,
+  KFMI_TRACE_KERNEL_TASK_STRANDS = 3, KFMI_TRACE_KERNEL_TASK_WORDS_SKIP = 4
+};
+int32_t kfmi_search_strands_trace(void *index, void *queries, void *results, uint32_t strands, uint32_t *trace);
+int32_t kfmi_search_seeds_trace(void *index, void *queries, void *intervals, void *spans, uint32_t max_seeds,
+                                uint32_t strands, uint32_t *trace);
+
 /* Diagnostic (not in the reference): replays the line requests a
  * task-mid / coop-mid search of `queries` makes (MID128 layout, K = 2, d = 64,
  * m % K == 0, both uploaded) without the LF chain's dependence: a trace launch

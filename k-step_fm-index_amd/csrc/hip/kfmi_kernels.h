@@ -202,17 +202,36 @@ __device__ __forceinline__ void fetch_ends_split(const IdxArgs& ix, const uint32
  * records what it does, and the type of the pointer it records through -- the
  * records of a launch (Trace) or an empty object (NoTrace, every search). */
 struct NoTrace {
-  static constexpr bool ON = false;
+  static constexpr bool ON = false, STRANDS = false;
   struct Out {};
   static Out from(uint4*) { return Out{}; }
   __device__ static Out at(Out, uint64_t) { return Out{}; }
 };
 struct Trace {
-  static constexpr bool ON = true;
+  static constexpr bool ON = true, STRANDS = false;
   typedef uint4* Out;
   static Out from(uint4* t) { return t; }
   __device__ static Out at(Out t, uint64_t q) { return t + q; }   /* read q's record */
 };
+/* Trace for the strand kernels (kfmi_search_strands_trace): launch_task_split
+ * picks task_strands_kernel / task_words_skip_kernel with it and nothing else,
+ * so the forward traced units (Trace) stay what they were. */
+struct StrandTrace : Trace {
+  static constexpr bool STRANDS = true;
+};
+
+/* Word 3 of the seed and strand trace records (kstep_fmi.h): which kernel ran,
+ * in which fetch form and with how many code registers, and the table
+ * settings it received.  KID: KFMI_TRACE_KERNEL_*. */
+template <int SPLIT, int MAXW, int KID>
+__device__ __forceinline__ uint32_t trace_launch_id(const IdxArgs& ix)
+{
+  const bool ft = ix.ftab != nullptr;
+  return (uint32_t) SPLIT | ((uint32_t) (MAXW / 8) << KFMI_TRACE_ID_MAXW_SHIFT) | ((uint32_t) KID << KFMI_TRACE_ID_KERNEL_SHIFT) |
+         ((ix.skip_split & 15u) << KFMI_TRACE_ID_SKIP_SPLIT_SHIFT) |
+         (ft && (ix.jump_split & JUMP_FTAB_FOLDED) ? (uint32_t) KFMI_TRACE_ID_FTAB_FOLDED : 0u) |
+         (ft ? ix.ftab_steps << KFMI_TRACE_ID_FTAB_STEPS_SHIFT : 0u);
+}
 
 /* The walk of the fused task kernel with the skip table (IdxArgs::skip,
  * DESIGN.md 5a'): every lane keeps its own step position `pos`, and each
@@ -456,13 +475,21 @@ __device__ __forceinline__ void skip_walk(const IdxArgs& ix, const uint32_t (&cw
  *   The loop ends when no lane has steps or free slots left; the segment that
  * reaches base 0 is stored then, and the slots a task did not use are zeroed.
  * Start: pos = 0 and [L, R), e from the caller -- the remainder-table entry
- * with e = m where it is not empty, else the full interval with e = mk. */
-template <class G, int MAXW, int SPLIT>
+ * with e = m where it is not empty, else the full interval with e = mk.
+ *   TR (kstep_fmi.h kfmi_search_seeds_trace): with Trace the same body counts
+ * the lane's K-steps, its lookups in either table by how they ended, the units
+ * that did not occur on their own and its records, and stores one 16-byte record
+ * with the caller's `ident` as word 3 when the walk is over.  Every hook is an
+ * `if constexpr (TR::ON)` block, as in skip_walk. */
+template <class G, int MAXW, int SPLIT, class TR = NoTrace>
 __device__ __forceinline__ void seed_walk(const IdxArgs& ix, const uint32_t (&cw)[MAXW], uint32_t steps, uint32_t mk,
                                           uint32_t Lq, uint32_t Rq, uint32_t e, uint32_t S, uint2* __restrict__ iv,
-                                          uint2* __restrict__ sp)
+                                          uint2* __restrict__ sp, typename TR::Out tr = typename TR::Out{},
+                                          [[maybe_unused]] uint32_t ident = 0u)
 {
   static_assert(G::K <= 2 && MAXW > 0, "seed search: task kernels at K <= 2");
+  /* TR: the record's words 0 .. 2; a remainder unit that does not occur (the caller's e == mk) is a lone unit */
+  [[maybe_unused]] uint32_t tr_walk = 0, tr_start = 0, tr_lone = ix.rem && e == mk ? 1u : 0u;
   extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
   const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
   uint32_t* cl = reinterpret_cast<uint32_t*>(stage) + wv * (64u * MAXW) + lane;
@@ -507,10 +534,12 @@ __device__ __forceinline__ void seed_walk(const IdxArgs& ix, const uint32_t (&cw
         L[0] = lf_stream<G>(ix, L[0], c[0], sx);
         R[0] = lf_stream<G>(ix, R[0], c[0], sx);
       }
+      if constexpr (TR::ON) tr_walk += KFMI_TRACE_STEP;
       if (R[0] <= L[0]) {   /* the segment ends at b */
         if (fresh) {        /* this unit alone does not occur: past it, no record */
           ++pos;
           e = b - (uint32_t) G::K;
+          if constexpr (TR::ON) ++tr_lone;
         } else {
           iv[cnt] = make_uint2(pL, pR);
           sp[cnt] = make_uint2(b, e - b);
@@ -529,8 +558,10 @@ __device__ __forceinline__ void seed_walk(const IdxArgs& ix, const uint32_t (&cw
         L[0] = te.x;
         R[0] = te.x + 1u;
         pos += J;
+        if constexpr (TR::ON) tr_walk += KFMI_TRACE_SKIP_HIT;
       } else {
         dead = true;
+        if constexpr (TR::ON) tr_walk += KFMI_TRACE_SKIP_MISS;
       }
     } else if (jump) {
       const FtabAt fe = ftab_entry_at(te, (ix.jump_split & JUMP_FTAB_FOLDED) != 0u, ix.bwtsize - 1u);
@@ -538,8 +569,10 @@ __device__ __forceinline__ void seed_walk(const IdxArgs& ix, const uint32_t (&cw
         L[0] = fe.L;
         R[0] = fe.R;
         pos += F;
+        if constexpr (TR::ON) tr_start += KFMI_SEED_TRACE_START_HIT;
       } else {
         dead = true;
+        if constexpr (TR::ON) tr_start += KFMI_SEED_TRACE_START_EMPTY;
       }
     }
   }
@@ -549,6 +582,7 @@ __device__ __forceinline__ void seed_walk(const IdxArgs& ix, const uint32_t (&cw
     sp[cnt] = make_uint2(b, e - b);
     ++cnt;
   }
+  if constexpr (TR::ON) *tr = make_uint4(tr_walk, tr_start, tr_lone | (cnt << KFMI_SEED_TRACE_RECORDS_SHIFT), ident);
   for (; cnt < S; ++cnt) {
     iv[cnt] = make_uint2(0u, 0u);
     sp[cnt] = make_uint2(0u, 0u);
@@ -678,11 +712,13 @@ __global__ __launch_bounds__(256) void task_kernel(IdxArgs ix, const uint32_t* _
  * word-major, 16 bases per word (K <= 2), at most MAXW words per task.  A lane
  * loads its column (a word row is consecutive tasks: coalesced) where the fused
  * kernel converts its ASCII row; the jump start, the remainder lookup and
- * skip_walk are the fused kernel's.  The forward kernels are not touched. */
-template <class G, int MAXW, int SPLIT>
+ * skip_walk are the fused kernel's.  The forward kernels are not touched.
+ * TR = StrandTrace (kfmi_search_strands_trace): skip_walk writes task q's record
+ * to trace[q] and the kernel replaces its word 3 by the launch identity. */
+template <class G, int MAXW, int SPLIT, class TR = NoTrace>
 __global__ __launch_bounds__(256) void task_words_skip_kernel(IdxArgs ix, const uint32_t* __restrict__ qp, uint64_t num,
                                                               uint32_t steps, uint32_t nwords,
-                                                              uint32_t* __restrict__ res)
+                                                              uint32_t* __restrict__ res, typename TR::Out trace)
 {
   static_assert(G::K <= 2 && MAXW > 0, "skip table: task kernels at K <= 2");
   const uint64_t q = (uint64_t) blockIdx.x * 256 + threadIdx.x;
@@ -702,7 +738,8 @@ __global__ __launch_bounds__(256) void task_words_skip_kernel(IdxArgs ix, const 
     L = lr.x;
     R = lr.y;
   }
-  skip_walk<G, MAXW, SPLIT>(ix, cw, steps, skip, L, R);
+  skip_walk<G, MAXW, SPLIT, false, TR>(ix, cw, steps, skip, L, R, TR::at(trace, q));
+  if constexpr (TR::ON) TR::at(trace, q)->w = trace_launch_id<SPLIT, MAXW, KFMI_TRACE_KERNEL_TASK_WORDS_SKIP>(ix);
   *reinterpret_cast<uint2*>(res + 2 * q) = make_uint2(L, R);
 }
 
@@ -750,11 +787,12 @@ __device__ __forceinline__ void stage_strand_codes(const uint8_t* __restrict__ a
  * of num reads, K <= 2, m % K == 0, m <= 16 * MAXW.  Only the staging differs
  * from task_kernel<G, 1, MAXW, SPLIT, true>: the jump start and skip_walk are
  * the same (without a skip table skip_walk takes every K-step from the code
- * words in LDS).  The forward kernels are not touched. */
-template <class G, int MAXW, int SPLIT>
+ * words in LDS).  The forward kernels are not touched.  TR: as for
+ * task_words_skip_kernel, task t's record at trace[t]. */
+template <class G, int MAXW, int SPLIT, class TR = NoTrace>
 __global__ __launch_bounds__(256) void task_strands_kernel(IdxArgs ix, const uint8_t* __restrict__ ascii, uint32_t m,
                                                            uint64_t num, uint32_t steps, uint32_t strands,
-                                                           uint32_t* __restrict__ res)
+                                                           uint32_t* __restrict__ res, typename TR::Out trace)
 {
   static_assert(G::K <= 2 && MAXW > 0, "strand staging: task kernels at K <= 2");
   extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
@@ -769,7 +807,8 @@ __global__ __launch_bounds__(256) void task_strands_kernel(IdxArgs ix, const uin
     L = lr.L;
     R = lr.R;
   }
-  skip_walk<G, MAXW, SPLIT>(ix, cw, steps, skip, L, R);
+  skip_walk<G, MAXW, SPLIT, false, TR>(ix, cw, steps, skip, L, R, TR::at(trace, t));
+  if constexpr (TR::ON) TR::at(trace, t)->w = trace_launch_id<SPLIT, MAXW, KFMI_TRACE_KERNEL_TASK_STRANDS>(ix);
   *reinterpret_cast<uint2*>(res + 2 * t) = make_uint2(L, R);
 }
 
@@ -777,11 +816,13 @@ __global__ __launch_bounds__(256) void task_strands_kernel(IdxArgs ix, const uin
  * walk.  The last rem bases are one unit: a remainder-table entry that is not
  * empty starts the first segment at base m, an empty one means that unit does
  * not occur and the walk starts past it.  The jump start is seed_walk's own
- * first round.  Slot t * S + s of either array is record s of task t. */
-template <class G, int MAXW, int SPLIT>
+ * first round.  Slot t * S + s of either array is record s of task t.
+ * TR = Trace: seed_walk's record of task t goes to trace[t], its word 3 the
+ * launch identity of the kernel KID (KFMI_TRACE_KERNEL_*). */
+template <class G, int MAXW, int SPLIT, int KID, class TR = NoTrace>
 __device__ __forceinline__ void seed_task(const IdxArgs& ix, const uint32_t (&cw)[MAXW], uint32_t rc, uint32_t m,
                                           uint32_t steps, uint64_t t, uint32_t S, uint32_t* __restrict__ res,
-                                          uint32_t* __restrict__ spans)
+                                          uint32_t* __restrict__ spans, typename TR::Out trace)
 {
   const uint32_t mk = m - ix.rem;
   uint32_t L = 0, R = ix.bwtsize, e = mk;
@@ -793,17 +834,23 @@ __device__ __forceinline__ void seed_task(const IdxArgs& ix, const uint32_t (&cw
       e = m;
     }
   }
-  seed_walk<G, MAXW, SPLIT>(ix, cw, steps, mk, L, R, e, S, reinterpret_cast<uint2*>(res) + t * S,
-                            reinterpret_cast<uint2*>(spans) + t * S);
+  if constexpr (TR::ON)
+    seed_walk<G, MAXW, SPLIT, TR>(ix, cw, steps, mk, L, R, e, S, reinterpret_cast<uint2*>(res) + t * S,
+                                  reinterpret_cast<uint2*>(spans) + t * S, TR::at(trace, t),
+                                  trace_launch_id<SPLIT, MAXW, KID>(ix));
+  else
+    seed_walk<G, MAXW, SPLIT>(ix, cw, steps, mk, L, R, e, S, reinterpret_cast<uint2*>(res) + t * S,
+                              reinterpret_cast<uint2*>(spans) + t * S);
 }
 
 /* The three seed kernels: an existing staging each, then seed_task.  They are
  * launched with or without a skip table.
  * Forward reads, fused packing: task_kernel's staging (m <= 16 * MAXW, any rem). */
-template <class G, int MAXW, int SPLIT>
+template <class G, int MAXW, int SPLIT, class TR = NoTrace>
 __global__ __launch_bounds__(256) void seed_kernel(IdxArgs ix, const uint8_t* __restrict__ ascii, uint32_t m,
                                                    uint64_t num, uint32_t steps, uint32_t S,
-                                                   uint32_t* __restrict__ res, uint32_t* __restrict__ spans)
+                                                   uint32_t* __restrict__ res, uint32_t* __restrict__ spans,
+                                                   typename TR::Out trace)
 {
   extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
   uint32_t cw[MAXW];
@@ -811,29 +858,31 @@ __global__ __launch_bounds__(256) void seed_kernel(IdxArgs ix, const uint8_t* __
   stage_query_codes<MAXW>(ascii, num, m, stage, cw, ix.rem, rc);   /* whole block, before any exit */
   const uint64_t t = (uint64_t) blockIdx.x * 256 + threadIdx.x;
   if (t >= num) return;
-  seed_task<G, MAXW, SPLIT>(ix, cw, rc, m, steps, t, S, res, spans);
+  seed_task<G, MAXW, SPLIT, KFMI_TRACE_KERNEL_SEED, TR>(ix, cw, rc, m, steps, t, S, res, spans, trace);
 }
 
 /* Either strand or both, fused packing: task_strands_kernel's staging (m % K == 0). */
-template <class G, int MAXW, int SPLIT>
+template <class G, int MAXW, int SPLIT, class TR = NoTrace>
 __global__ __launch_bounds__(256) void seed_strands_kernel(IdxArgs ix, const uint8_t* __restrict__ ascii, uint32_t m,
                                                            uint64_t num, uint32_t steps, uint32_t strands, uint32_t S,
-                                                           uint32_t* __restrict__ res, uint32_t* __restrict__ spans)
+                                                           uint32_t* __restrict__ res, uint32_t* __restrict__ spans,
+                                                           typename TR::Out trace)
 {
   extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
   uint32_t cw[MAXW];
   stage_strand_codes<MAXW>(ascii, num, m, stage, cw, strands);   /* whole block, before any exit */
   const uint64_t t = (uint64_t) blockIdx.x * 256 + threadIdx.x;
   if (t >= (strands == 3u ? 2u : 1u) * num) return;
-  seed_task<G, MAXW, SPLIT>(ix, cw, 0u, m, steps, t, S, res, spans);
+  seed_task<G, MAXW, SPLIT, KFMI_TRACE_KERNEL_SEED_STRANDS, TR>(ix, cw, 0u, m, steps, t, S, res, spans, trace);
 }
 
 /* Code words a pack launch or the host wrote (num task columns of qp, row
  * nwords the remainder codes): task_words_skip_kernel's loads. */
-template <class G, int MAXW, int SPLIT>
+template <class G, int MAXW, int SPLIT, class TR = NoTrace>
 __global__ __launch_bounds__(256) void seed_words_kernel(IdxArgs ix, const uint32_t* __restrict__ qp, uint32_t m,
                                                          uint64_t num, uint32_t steps, uint32_t nwords, uint32_t S,
-                                                         uint32_t* __restrict__ res, uint32_t* __restrict__ spans)
+                                                         uint32_t* __restrict__ res, uint32_t* __restrict__ spans,
+                                                         typename TR::Out trace)
 {
   const uint64_t t = (uint64_t) blockIdx.x * 256 + threadIdx.x;
   if (t >= num) return;
@@ -841,7 +890,7 @@ __global__ __launch_bounds__(256) void seed_words_kernel(IdxArgs ix, const uint3
 #pragma unroll
   for (int k = 0; k < MAXW; ++k) cw[k] = (uint32_t) k < nwords ? qp[(uint64_t) k * num + t] : 0u;
   const uint32_t rc = ix.rem ? qp[(uint64_t) nwords * num + t] & ((1u << (2u * ix.rem)) - 1u) : 0u;
-  seed_task<G, MAXW, SPLIT>(ix, cw, rc, m, steps, t, S, res, spans);
+  seed_task<G, MAXW, SPLIT, KFMI_TRACE_KERNEL_SEED_WORDS, TR>(ix, cw, rc, m, steps, t, S, res, spans, trace);
 }
 
 /* ftab construction: [L, R) of every code stream v of ftab_steps K-steps
@@ -1239,7 +1288,8 @@ struct SearchLaunch {
   /* text jump, the line table (Op::JumpLines): jump_isa and jump_words words of jump_text of a num-base text ->
      jump_line_count(num) lines at jump_lines */
   uint32_t* jump_lines;
-  /* walk trace (trace_one): num records, one per read; null in every other launch */
+  /* walk trace (trace_one, strands_trace_one, seeds_trace_one): one record per read or task; null in every
+     other launch */
   uint4* trace;
 };
 
@@ -1247,7 +1297,9 @@ struct SearchLaunch {
  * traced kernels, which exist for what the text jump serves -- the fused
  * forward walk on the plain layouts at K <= 2; there a search without any table
  * takes the tables' kernel too, so that skip_walk records its plain steps.
- * The caller has refused everything else. */
+ * TR = StrandTrace (kfmi_search_strands_trace, strands_trace_one below): the
+ * strand kernels' traced forms and nothing else -- the plain walk of packed
+ * words has none.  The caller has refused everything else. */
 template <class G, int SPLIT, class TR = NoTrace>
 static void launch_task_split(const SearchLaunch& a)
 {
@@ -1256,70 +1308,73 @@ static void launch_task_split(const SearchLaunch& a)
   const typename TR::Out tr = TR::from(a.trace);
   if (a.maxw) {
     const size_t lds = 4 * (size_t) stage_slot_bytes(a.m);
-    if constexpr (G::K <= 2 && !TR::ON) {
+    if constexpr (G::K <= 2 && (!TR::ON || TR::STRANDS)) {
       if (a.strands) {   /* strand-aware staging, then the fused kernel's own walk */
         const uint64_t tblocks = ((a.strands == 3u ? 2u : 1u) * a.num + 255) / 256;
         const size_t lds_str = std::max(lds, (size_t) 4 * 64 * 4 * (size_t) a.maxw);
         if (a.maxw == 8)
-          hipLaunchKernelGGL((task_strands_kernel<G, 8, SPLIT>), dim3((uint32_t) tblocks), dim3(256), lds_str, a.st,
-                             a.ix, a.ascii, a.m, a.num, a.steps, a.strands, a.res);
+          hipLaunchKernelGGL((task_strands_kernel<G, 8, SPLIT, TR>), dim3((uint32_t) tblocks), dim3(256), lds_str, a.st,
+                             a.ix, a.ascii, a.m, a.num, a.steps, a.strands, a.res, tr);
         else
-          hipLaunchKernelGGL((task_strands_kernel<G, 16, SPLIT>), dim3((uint32_t) tblocks), dim3(256), lds_str, a.st,
-                             a.ix, a.ascii, a.m, a.num, a.steps, a.strands, a.res);
+          hipLaunchKernelGGL((task_strands_kernel<G, 16, SPLIT, TR>), dim3((uint32_t) tblocks), dim3(256), lds_str, a.st,
+                             a.ix, a.ascii, a.m, a.num, a.steps, a.strands, a.res, tr);
         return;
       }
     }
-    const uint64_t blocks = (a.num + 255) / 256;
-    if constexpr (G::K <= 2) {
-      if (TR::ON || a.ix.skip || a.ix.jsa) {   /* the walk with the tables; LDS: the staging, then 64 x maxw code words per wave */
-        const size_t lds_skip = std::max(lds, (size_t) 4 * 64 * 4 * (size_t) a.maxw);
-        if constexpr (G::LAY == LAY_INTER || G::LAY == LAY_MID) {
-          if (a.ix.jsa) {   /* with the text jump (DESIGN.md 5a'') */
-            IdxArgs ix = a.ix;
-            if ((ix.jump_split & JUMP_LINES_GROUPED) && a.m > JUMP_LINES_GROUPED_MAX_M)
-              ix.jump_split &= ~(JUMP_LINES | JUMP_LINES_GROUPED);   /* long reads: the flat tables' form is faster */
-            if (a.maxw == 8)
-              hipLaunchKernelGGL((task_kernel<G, 1, 8, SPLIT, true, true, TR>), dim3((uint32_t) blocks), dim3(256),
-                                 lds_skip, a.st, ix, a.qp, a.ascii, a.m, a.num, a.steps, a.nwords, a.res, tr);
-            else
-              hipLaunchKernelGGL((task_kernel<G, 1, 16, SPLIT, true, true, TR>), dim3((uint32_t) blocks), dim3(256),
-                                 lds_skip, a.st, ix, a.qp, a.ascii, a.m, a.num, a.steps, a.nwords, a.res, tr);
-            return;
+    if constexpr (!TR::STRANDS) {   /* that policy has the strand kernels only (the caller refused the rest) */
+      const uint64_t blocks = (a.num + 255) / 256;
+      if constexpr (G::K <= 2) {
+        if (TR::ON || a.ix.skip || a.ix.jsa) {   /* the walk with the tables; LDS: the staging, then 64 x maxw code words per wave */
+          const size_t lds_skip = std::max(lds, (size_t) 4 * 64 * 4 * (size_t) a.maxw);
+          if constexpr (G::LAY == LAY_INTER || G::LAY == LAY_MID) {
+            if (a.ix.jsa) {   /* with the text jump (DESIGN.md 5a'') */
+              IdxArgs ix = a.ix;
+              if ((ix.jump_split & JUMP_LINES_GROUPED) && a.m > JUMP_LINES_GROUPED_MAX_M)
+                ix.jump_split &= ~(JUMP_LINES | JUMP_LINES_GROUPED);   /* long reads: the flat tables' form is faster */
+              if (a.maxw == 8)
+                hipLaunchKernelGGL((task_kernel<G, 1, 8, SPLIT, true, true, TR>), dim3((uint32_t) blocks), dim3(256),
+                                   lds_skip, a.st, ix, a.qp, a.ascii, a.m, a.num, a.steps, a.nwords, a.res, tr);
+              else
+                hipLaunchKernelGGL((task_kernel<G, 1, 16, SPLIT, true, true, TR>), dim3((uint32_t) blocks), dim3(256),
+                                   lds_skip, a.st, ix, a.qp, a.ascii, a.m, a.num, a.steps, a.nwords, a.res, tr);
+              return;
+            }
           }
+          if (a.maxw == 8)
+            hipLaunchKernelGGL((task_kernel<G, 1, 8, SPLIT, true, false, TR>), dim3((uint32_t) blocks), dim3(256), lds_skip,
+                               a.st, a.ix, a.qp, a.ascii, a.m, a.num, a.steps, a.nwords, a.res, tr);
+          else
+            hipLaunchKernelGGL((task_kernel<G, 1, 16, SPLIT, true, false, TR>), dim3((uint32_t) blocks), dim3(256), lds_skip,
+                               a.st, a.ix, a.qp, a.ascii, a.m, a.num, a.steps, a.nwords, a.res, tr);
+          return;
         }
+      }
+      if constexpr (!TR::ON) {
         if (a.maxw == 8)
-          hipLaunchKernelGGL((task_kernel<G, 1, 8, SPLIT, true, false, TR>), dim3((uint32_t) blocks), dim3(256), lds_skip,
-                             a.st, a.ix, a.qp, a.ascii, a.m, a.num, a.steps, a.nwords, a.res, tr);
+          hipLaunchKernelGGL((task_kernel<G, 1, 8, SPLIT>), dim3((uint32_t) blocks), dim3(256), lds, a.st, a.ix, a.qp,
+                             a.ascii, a.m, a.num, a.steps, a.nwords, a.res, tr);
         else
-          hipLaunchKernelGGL((task_kernel<G, 1, 16, SPLIT, true, false, TR>), dim3((uint32_t) blocks), dim3(256), lds_skip,
-                             a.st, a.ix, a.qp, a.ascii, a.m, a.num, a.steps, a.nwords, a.res, tr);
-        return;
+          hipLaunchKernelGGL((task_kernel<G, 1, 16, SPLIT>), dim3((uint32_t) blocks), dim3(256), lds, a.st, a.ix, a.qp,
+                             a.ascii, a.m, a.num, a.steps, a.nwords, a.res, tr);
       }
     }
-    if constexpr (!TR::ON) {
-      if (a.maxw == 8)
-        hipLaunchKernelGGL((task_kernel<G, 1, 8, SPLIT>), dim3((uint32_t) blocks), dim3(256), lds, a.st, a.ix, a.qp,
-                           a.ascii, a.m, a.num, a.steps, a.nwords, a.res, tr);
-      else
-        hipLaunchKernelGGL((task_kernel<G, 1, 16, SPLIT>), dim3((uint32_t) blocks), dim3(256), lds, a.st, a.ix, a.qp,
-                           a.ascii, a.m, a.num, a.steps, a.nwords, a.res, tr);
-    }
-  } else if constexpr (!TR::ON) {
+  } else if constexpr (!TR::ON || TR::STRANDS) {
     const uint64_t blocks = (a.num + 255) / 256;
     if constexpr (G::K <= 2) {
       if (a.ix.skip && a.words_maxw) {   /* strand searches: the skip-table walk on packed words */
         const size_t lds_skip = (size_t) 4 * 64 * 4 * (size_t) a.words_maxw;
         if (a.words_maxw == 8)
-          hipLaunchKernelGGL((task_words_skip_kernel<G, 8, SPLIT>), dim3((uint32_t) blocks), dim3(256), lds_skip, a.st,
-                             a.ix, a.qp, a.num, a.steps, a.nwords, a.res);
+          hipLaunchKernelGGL((task_words_skip_kernel<G, 8, SPLIT, TR>), dim3((uint32_t) blocks), dim3(256), lds_skip,
+                             a.st, a.ix, a.qp, a.num, a.steps, a.nwords, a.res, tr);
         else
-          hipLaunchKernelGGL((task_words_skip_kernel<G, 16, SPLIT>), dim3((uint32_t) blocks), dim3(256), lds_skip,
-                             a.st, a.ix, a.qp, a.num, a.steps, a.nwords, a.res);
+          hipLaunchKernelGGL((task_words_skip_kernel<G, 16, SPLIT, TR>), dim3((uint32_t) blocks), dim3(256), lds_skip,
+                             a.st, a.ix, a.qp, a.num, a.steps, a.nwords, a.res, tr);
         return;
       }
     }
-    hipLaunchKernelGGL((task_kernel<G, 1, 0, SPLIT>), dim3((uint32_t) blocks), dim3(256), 0, a.st, a.ix, a.qp,
-                       a.ascii, a.m, a.num, a.steps, a.nwords, a.res, tr);
+    if constexpr (!TR::ON)
+      hipLaunchKernelGGL((task_kernel<G, 1, 0, SPLIT>), dim3((uint32_t) blocks), dim3(256), 0, a.st, a.ix, a.qp,
+                         a.ascii, a.m, a.num, a.steps, a.nwords, a.res, tr);
   }
 }
 
@@ -1351,15 +1406,16 @@ static hipError_t launch_task(const SearchLaunch& a)
 /* Seed searches: the kernel by where the code words come from -- fused packing
  * (a.maxw; a.strands 2 / 3 the strand staging on a.num reads), else the
  * a.num task columns in a.qp (a.words_maxw registers). */
-template <class G, int SPLIT>
+template <class G, int SPLIT, class TR = NoTrace>
 static void launch_seeds_split(const SearchLaunch& a)
 {
+  const typename TR::Out tr = TR::from(a.trace);
 #define KFMI_SEED_MAXW(MW, KERNEL, GRID, LDS, ...)                                                           \
   do {                                                                                                       \
     if ((MW) == 8)                                                                                           \
-      hipLaunchKernelGGL((KERNEL<G, 8, SPLIT>), dim3((uint32_t) (GRID)), dim3(256), LDS, a.st, __VA_ARGS__); \
+      hipLaunchKernelGGL((KERNEL<G, 8, SPLIT, TR>), dim3((uint32_t) (GRID)), dim3(256), LDS, a.st, __VA_ARGS__, tr); \
     else                                                                                                     \
-      hipLaunchKernelGGL((KERNEL<G, 16, SPLIT>), dim3((uint32_t) (GRID)), dim3(256), LDS, a.st, __VA_ARGS__); \
+      hipLaunchKernelGGL((KERNEL<G, 16, SPLIT, TR>), dim3((uint32_t) (GRID)), dim3(256), LDS, a.st, __VA_ARGS__, tr); \
   } while (0)
   if (a.maxw) {   /* LDS: the staging, then 64 x maxw code words per wave */
     const size_t lds = std::max((size_t) 4 * stage_slot_bytes(a.m), (size_t) 4 * 64 * 4 * (size_t) a.maxw);
@@ -1379,8 +1435,9 @@ static void launch_seeds_split(const SearchLaunch& a)
 #undef KFMI_SEED_MAXW
 }
 
-/* The fetch form is launch_task's for the same geometry and table size class. */
-template <class G>
+/* The fetch form is launch_task's for the same geometry and table size class.
+ * TR = Trace (kfmi_search_seeds_trace): the same choices with the traced kernels. */
+template <class G, class TR = NoTrace>
 static hipError_t launch_seeds(const SearchLaunch& a)
 {
   if constexpr (G::K <= 2 && (G::LAY == LAY_INTER || G::LAY == LAY_MID)) {
@@ -1388,13 +1445,13 @@ static hipError_t launch_seeds(const SearchLaunch& a)
     if (mw != 8 && mw != 16) return hipErrorInvalidValue;
     const uint32_t want = a.ix.split;
     if constexpr (G::SMALL && X4<G>::OK) {   /* each geometry gets only the forms it can be launched with */
-      if (want == 1) launch_seeds_split<G, 8>(a);
-      else launch_seeds_split<G, 7>(a);
+      if (want == 1) launch_seeds_split<G, 8, TR>(a);
+      else launch_seeds_split<G, 7, TR>(a);
     } else if constexpr (G::SMALL) {
-      if (want == 4 || (want == 2 && mw == 8)) launch_seeds_split<G, 4>(a);
-      else launch_seeds_split<G, 1>(a);
+      if (want == 4 || (want == 2 && mw == 8)) launch_seeds_split<G, 4, TR>(a);
+      else launch_seeds_split<G, 1, TR>(a);
     } else {
-      launch_seeds_split<G, 1>(a);
+      launch_seeds_split<G, 1, TR>(a);
     }
     return hipGetLastError();
   } else {
@@ -1593,6 +1650,31 @@ hipError_t trace_one(const SearchLaunch& a)
 
 #define KFMI_TRACE_INSTANTIATE(KK, NBV, LAYV) template hipError_t trace_one<KK, NBV, LAYV>(const SearchLaunch&);
 #define KFMI_TRACE_EXTERN(KK, NBV, LAYV) extern template hipError_t trace_one<KK, NBV, LAYV>(const SearchLaunch&);
+
+/* The traced strand and seed kernels' launches (kfmi_search_strands_trace,
+ * kfmi_search_seeds_trace): launch_task / launch_seeds with the traced kernels,
+ * instantiated per (K, NB, LAY) in kfmi_inst_trace_seeds_*.hip for K <= 2 on the
+ * task and task-mid layouts, called from kfmi_strands.hip and kfmi_seeds.hip. */
+template <int K, int NB, int LAY>
+hipError_t strands_trace_one(const SearchLaunch& a)
+{
+  if (!a.trace || (a.maxw ? !a.strands : !(a.ix.skip && a.words_maxw))) return hipErrorInvalidValue;
+  return launch_task<Geo<K, NB, LAY>, StrandTrace>(a);
+}
+
+template <int K, int NB, int LAY>
+hipError_t seeds_trace_one(const SearchLaunch& a)
+{
+  if (!a.trace) return hipErrorInvalidValue;
+  return launch_seeds<Geo<K, NB, LAY>, Trace>(a);
+}
+
+#define KFMI_SEEDS_TRACE_INSTANTIATE(KK, NBV, LAYV)                             \
+  template hipError_t strands_trace_one<KK, NBV, LAYV>(const SearchLaunch&); \
+  template hipError_t seeds_trace_one<KK, NBV, LAYV>(const SearchLaunch&);
+#define KFMI_SEEDS_TRACE_EXTERN(KK, NBV, LAYV)                                         \
+  extern template hipError_t strands_trace_one<KK, NBV, LAYV>(const SearchLaunch&); \
+  extern template hipError_t seeds_trace_one<KK, NBV, LAYV>(const SearchLaunch&);
 
 }  // namespace kfmi
 

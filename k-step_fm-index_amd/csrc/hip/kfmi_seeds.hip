@@ -27,11 +27,18 @@ KFMI_FOR_NB(KFMI_SEEDS_EXTERN, 1, LAY_INTER)
 KFMI_FOR_NB(KFMI_SEEDS_EXTERN, 2, LAY_INTER)
 KFMI_FOR_NB(KFMI_SEEDS_EXTERN, 1, LAY_MID)
 KFMI_FOR_NB(KFMI_SEEDS_EXTERN, 2, LAY_MID)
+/* seeds_trace_one<K, NB, LAY> is compiled in kfmi_inst_trace_seeds_*.hip */
+KFMI_FOR_NB(KFMI_SEEDS_TRACE_EXTERN, 1, LAY_INTER)
+KFMI_FOR_NB(KFMI_SEEDS_TRACE_EXTERN, 2, LAY_INTER)
+KFMI_FOR_NB(KFMI_SEEDS_TRACE_EXTERN, 1, LAY_MID)
+KFMI_FOR_NB(KFMI_SEEDS_TRACE_EXTERN, 2, LAY_MID)
 
+/* a.trace set: the traced kernels (kfmi_search_seeds_trace) */
 static hipError_t dispatch_seeds(uint32_t K, uint32_t nb, int lay, const SearchLaunch& a)
 {
-#define KFMI_CASE(KK, NBV, LAYV) \
-  if (K == KK && nb == NBV && lay == LAYV) return seeds_one<KK, NBV, LAYV>(a);
+#define KFMI_CASE(KK, NBV, LAYV)                \
+  if (K == KK && nb == NBV && lay == LAYV)      \
+    return a.trace ? seeds_trace_one<KK, NBV, LAYV>(a) : seeds_one<KK, NBV, LAYV>(a);
   KFMI_FOR_NB(KFMI_CASE, 1, LAY_INTER)
   KFMI_FOR_NB(KFMI_CASE, 2, LAY_INTER)
   KFMI_FOR_NB(KFMI_CASE, 1, LAY_MID)
@@ -52,10 +59,11 @@ static bool seeds_supported(const kfmi_dev_index* di)
  * the device, fused packing on), else walk dq->packed -- written by the pack
  * launch here, or by the host on upload.  Reverse and both-strand tasks pack
  * in the kernel where a strand search would (strand_fused_maxw), else walk
- * the strand pack's task columns. */
+ * the strand pack's task columns.  trace: null, or one record per task for the
+ * traced kernels (kfmi_search_seeds_trace); nothing else differs. */
 static int32_t seeds_enqueue(kfmi_dev_index* di, kfmi_dev_queries* dq, uint32_t* d_iv, uint32_t* d_sp, hipStream_t st,
                              hipEvent_t* ev, const TableWants& want, uint32_t max_seeds, uint32_t strands,
-                             DevCtx* ctx)
+                             DevCtx* ctx, uint4* trace = nullptr)
 {
   if (dq->device != di->device || dq->K != di->K) return KFMI_E_BAD_ARGUMENT;
   const bool fwd = strands == KFMI_STRAND_FWD;
@@ -85,6 +93,7 @@ static int32_t seeds_enqueue(kfmi_dev_index* di, kfmi_dev_queries* dq, uint32_t*
   a.res = d_iv;
   a.spans = d_sp;
   a.max_seeds = max_seeds;
+  a.trace = trace;
   HIP_OK(hipEventRecord(ev[0], st));
   if (!a.maxw) HIP_OK(fwd ? launch_pack(dq, st) : launch_strand_pack(dq, dq->strand_words, strands, false, st));
   HIP_OK(hipEventRecord(ev[1], st));
@@ -93,8 +102,11 @@ static int32_t seeds_enqueue(kfmi_dev_index* di, kfmi_dev_queries* dq, uint32_t*
   return KFMI_SUCCESS;
 }
 
-extern "C" int32_t kfmi_search_seeds(void* index, void* queries, void* intervals, void* spans, uint32_t max_seeds,
-                                     uint32_t strands)
+/* kfmi_search_seeds, and kfmi_search_seeds_trace when `trace` is given: the
+ * same checks in the same order, the same enqueue; the traced call adds the
+ * device records and their copy to the host. */
+static int32_t search_seeds(void* index, void* queries, void* intervals, void* spans, uint32_t max_seeds,
+                            uint32_t strands, uint32_t* trace)
 {
   if (max_seeds < 1 || max_seeds > 8) return KFMI_E_BAD_ARGUMENT;
   if (strands < KFMI_STRAND_FWD || strands > KFMI_STRAND_BOTH) return KFMI_E_BAD_ARGUMENT;
@@ -116,11 +128,37 @@ extern "C" int32_t kfmi_search_seeds(void* index, void* queries, void* intervals
   if (ri->d_device != di->device || rs->d_device != di->device) return KFMI_E_BAD_ARGUMENT;
   SearchLane l;
   int32_t err = search_lane(di->device, &l);
-  if (!err)   /* a seed search never takes the text jump */
-    err = seeds_enqueue(di, q->dev, ri->d_results, rs->d_results, l.st, l.ev, tables_wanted().no_jump(), max_seeds,
-                        strands, l.ctx);
+  if (err) return err;
+  const uint64_t tasks = (strands == KFMI_STRAND_BOTH ? 2u : 1u) * q->num;
+  uint4* d_trace = nullptr;
+  if (trace && hipMalloc((void**) &d_trace, 16ull * (tasks ? tasks : 1)) != hipSuccess) {
+    (void) hipGetLastError();
+    return KFMI_E_DEVICE_ALLOC;
+  }
+  /* a seed search never takes the text jump */
+  err = seeds_enqueue(di, q->dev, ri->d_results, rs->d_results, l.st, l.ev, tables_wanted().no_jump(), max_seeds, strands,
+                      l.ctx, d_trace);
   if (!err) err = search_finish(l.st, l.ev, t_ms);
+  if (trace) {
+    if (!err && tasks && hipMemcpy(trace, d_trace, 16ull * tasks, hipMemcpyDeviceToHost) != hipSuccess) err = KFMI_E_KERNEL;
+    (void) hipFree(d_trace);
+  }
   return err;
+}
+
+extern "C" int32_t kfmi_search_seeds(void* index, void* queries, void* intervals, void* spans, uint32_t max_seeds,
+                                     uint32_t strands)
+{
+  return search_seeds(index, queries, intervals, spans, max_seeds, strands, nullptr);
+}
+
+/* kstep_fmi.h: kfmi_search_seeds with the traced kernels and one record per
+ * task copied out. */
+extern "C" int32_t kfmi_search_seeds_trace(void* index, void* queries, void* intervals, void* spans, uint32_t max_seeds,
+                                           uint32_t strands, uint32_t* trace)
+{
+  if (!trace) return KFMI_E_BAD_ARGUMENT;
+  return search_seeds(index, queries, intervals, spans, max_seeds, strands, trace);
 }
 
 }  // namespace kfmi

@@ -31,6 +31,24 @@
 
 namespace kfmi {
 
+/* strands_trace_one<K, NB, LAY> is compiled in kfmi_inst_trace_seeds_*.hip */
+KFMI_FOR_NB(KFMI_SEEDS_TRACE_EXTERN, 1, LAY_INTER)
+KFMI_FOR_NB(KFMI_SEEDS_TRACE_EXTERN, 2, LAY_INTER)
+KFMI_FOR_NB(KFMI_SEEDS_TRACE_EXTERN, 1, LAY_MID)
+KFMI_FOR_NB(KFMI_SEEDS_TRACE_EXTERN, 2, LAY_MID)
+
+static hipError_t dispatch_strands_trace(uint32_t K, uint32_t nb, int lay, const SearchLaunch& a)
+{
+#define KFMI_CASE(KK, NBV, LAYV) \
+  if (K == KK && nb == NBV && lay == LAYV) return strands_trace_one<KK, NBV, LAYV>(a);
+  KFMI_FOR_NB(KFMI_CASE, 1, LAY_INTER)
+  KFMI_FOR_NB(KFMI_CASE, 2, LAY_INTER)
+  KFMI_FOR_NB(KFMI_CASE, 1, LAY_MID)
+  KFMI_FOR_NB(KFMI_CASE, 2, LAY_MID)
+#undef KFMI_CASE
+  return hipErrorInvalidValue;
+}
+
 /* ASCII [num][m] -> code words of the ns * num tasks, word w of task t at
  * out[w * ns * num + t] and the remainder codes in row nwords, the layout the
  * LF kernels read with ns * num queries.  A block takes tq reads, staged
@@ -286,9 +304,14 @@ int strand_fused_maxw(const kfmi_dev_index* di, bool ascii, uint32_t K, uint32_t
  * walk is the fused kernel's.  Else the strand pack, then the backend's LF
  * kernel on the ns * num task columns (codes from words: MAXW == 0, so the
  * forward kernels run as they are; with the skip table in effect the task
- * backends walk the words with it, task_words_skip_kernel). */
+ * backends walk the words with it, task_words_skip_kernel).  trace: null, or
+ * one record per task for the traced strand kernels (kfmi_search_strands_trace,
+ * whose caller has refused the backends that have none); the plain walk of
+ * packed words has no traced form and is refused here, before anything is
+ * queued. */
 static int32_t strands_enqueue(kfmi_dev_index* di, kfmi_dev_queries* dq, uint32_t* d_res, hipStream_t st,
-                               hipEvent_t* ev, const TableWants& want, uint32_t strands, DevCtx* ctx)
+                               hipEvent_t* ev, const TableWants& want, uint32_t strands, DevCtx* ctx,
+                               uint4* trace = nullptr)
 {
   if (dq->device != di->device || dq->K != di->K) return KFMI_E_BAD_ARGUMENT;
   if (!dq->ascii && dq->K == 3) return KFMI_E_BAD_ARGUMENT;
@@ -299,12 +322,13 @@ static int32_t strands_enqueue(kfmi_dev_index* di, kfmi_dev_queries* dq, uint32_
   int32_t err = use_tables(di, st, a.ix, want, dq->rem);
   if (err) return err;
   a.maxw = strand_fused_maxw(di, dq->ascii != nullptr, dq->K, dq->steps, dq->rem);
+  a.words_maxw = a.maxw ? 0 : strand_words_maxw(dq->nwords);
+  if (trace && !a.maxw && !(a.ix.skip && a.words_maxw)) return KFMI_E_NOT_IMPLEMENTED;   /* task_kernel<G, 1, 0, SPLIT> */
   if (!a.maxw) {
     err = strand_reserve(dq, dq->num, ctx);
     if (err) return err;
   }
   a.strands = a.maxw ? strands : 0u;
-  a.words_maxw = a.maxw ? 0 : strand_words_maxw(dq->nwords);
   a.qp = dq->strand_words;
   a.ascii = dq->ascii;
   a.m = dq->size;
@@ -312,12 +336,13 @@ static int32_t strands_enqueue(kfmi_dev_index* di, kfmi_dev_queries* dq, uint32_
   a.steps = dq->steps;
   a.nwords = dq->nwords;
   a.res = d_res;
+  a.trace = trace;
   HIP_OK(hipEventRecord(ev[0], st));
   if (!a.maxw) HIP_OK(launch_strand_pack(dq, dq->strand_words, strands, false, st));
   HIP_OK(hipEventRecord(ev[1], st));
   if (dq->num) {
     const Op op = is_coop(di->backend) ? Op::Coop : Op::Task;
-    HIP_OK(dispatch(op, di->K, di->nb, di->layout, a));
+    HIP_OK(trace ? dispatch_strands_trace(di->K, di->nb, di->layout, a) : dispatch(op, di->K, di->nb, di->layout, a));
   }
   HIP_OK(hipEventRecord(ev[2], st));
   return KFMI_SUCCESS;
@@ -345,6 +370,44 @@ extern "C" int32_t kfmi_search_strands(void* index, void* queries, void* results
   const TableWants want = tables_wanted().no_jump();   /* a strand search never takes the text jump */
   if (!err) err = strands_enqueue(di, q->dev, r->d_results, l.st, l.ev, want, strands, l.ctx);
   if (!err) err = search_finish(l.st, l.ev, t_ms);
+  return err;
+}
+
+/* kstep_fmi.h: kfmi_search_strands (REV, BOTH) on resident single-device
+ * handles with the traced strand kernels -- strands_enqueue itself, so the
+ * tables, the staging, the fetch form and the launch rules are the search's
+ * own -- and one record per task copied out.  Everything that has no traced
+ * kernel is refused before anything is queued. */
+extern "C" int32_t kfmi_search_strands_trace(void* index, void* queries, void* results, uint32_t strands,
+                                             uint32_t* trace)
+{
+  if (strands != KFMI_STRAND_REV && strands != KFMI_STRAND_BOTH) return KFMI_E_BAD_ARGUMENT;
+  kfmi_fmi_t* f = (kfmi_fmi_t*) index;
+  kfmi_qrys_t* q = (kfmi_qrys_t*) queries;
+  kfmi_res_t* r = (kfmi_res_t*) results;
+  if (!f || !q || !r || !trace) return KFMI_E_BAD_ARGUMENT;
+  const uint64_t tasks = (strands == KFMI_STRAND_BOTH ? 2u : 1u) * q->num;
+  if (r->num != tasks) return KFMI_E_BAD_ARGUMENT;
+  DeviceGuard dg;
+  std::shared_lock<RwLock> lk(index_lock(f));
+  if (f->grp || q->grp || r->grp) return KFMI_E_NOT_IMPLEMENTED;
+  if (!f->dev || !q->dev || !r->d_results) return KFMI_E_NOT_ON_DEVICE;
+  kfmi_dev_index* di = f->dev;
+  if (r->d_device != di->device) return KFMI_E_BAD_ARGUMENT;
+  if (is_coop(di->backend) || (di->layout != LAY_INTER && di->layout != LAY_MID) || di->K < 1 || di->K > 2)
+    return KFMI_E_NOT_IMPLEMENTED;
+  SearchLane l;
+  int32_t err = search_lane(di->device, &l);
+  if (err) return err;
+  uint4* d_trace = nullptr;
+  if (hipMalloc((void**) &d_trace, 16ull * (tasks ? tasks : 1)) != hipSuccess) {
+    (void) hipGetLastError();
+    return KFMI_E_DEVICE_ALLOC;
+  }
+  err = strands_enqueue(di, q->dev, r->d_results, l.st, l.ev, tables_wanted().no_jump(), strands, l.ctx, d_trace);
+  if (!err) err = search_finish(l.st, l.ev, t_ms);
+  if (!err && tasks && hipMemcpy(trace, d_trace, 16ull * tasks, hipMemcpyDeviceToHost) != hipSuccess) err = KFMI_E_KERNEL;
+  (void) hipFree(d_trace);
   return err;
 }
 

@@ -168,6 +168,8 @@ def load() -> ctypes.CDLL:
         "kfmi_search_seeds": (i32, [vp, vp, vp, vp, u32, u32]),
         "kfmi_search_seeds_cpu": (i32, [vp, vp, vp, vp, u32, u32, i32]),
         "kfmi_search_trace": (i32, [vp, vp, vp, vp]),
+        "kfmi_search_strands_trace": (i32, [vp, vp, vp, u32, vp]),
+        "kfmi_search_seeds_trace": (i32, [vp, vp, vp, vp, u32, u32, vp]),
         "kfmi_results_to_device": (i32, [vp]),
         "kfmi_verify_seeds": (i32, [vp, vp, vp, vp, vp, u32, u32, u32, u32]),
         "kfmi_verify_seeds_cpu": (i32, [vp, u64, vp, u64, vp, vp, vp, vp, u32, u32, u32, u32, i32]),
@@ -1020,6 +1022,94 @@ def search_seeds_array(index: Index, reads: np.ndarray, backend: str | None = No
             transfer_to_cpu(sp)
         shape = (_strand_count(strands) * n, s, 2)
         return iv.array().copy().reshape(shape), sp.array().copy().reshape(shape)
+    finally:
+        q.close()
+        iv.close()
+        sp.close()
+
+
+SEED_TRACE_FIELDS = ("steps", "skip_hits", "skip_misses", "start_hits", "start_empty", "lone_units", "records")
+TRACE_KERNELS = ("seed_kernel", "seed_strands_kernel", "seed_words_kernel", "task_strands_kernel",
+                 "task_words_skip_kernel")
+LAUNCH_ID_FIELDS = ("form", "maxw", "kernel", "skip_split", "ftab_folded", "ftab_steps")
+
+
+def decode_seed_trace(records: np.ndarray) -> dict:
+    """The named fields of words 0 .. 2 of kfmi_search_seeds_trace's records
+    (uint32 [T, 4], kstep_fmi.h): int64 arrays of T per name in
+    SEED_TRACE_FIELDS.  decode_launch_id names word 3."""
+    r = np.asarray(records, dtype=np.uint32).reshape(-1, 4).astype(np.int64)
+    return {
+        "steps": r[:, 0] & 0xFFFF,
+        "skip_hits": (r[:, 0] >> 16) & 0xFF,
+        "skip_misses": (r[:, 0] >> 24) & 0xFF,
+        "start_hits": r[:, 1] & 0xFFFF,
+        "start_empty": (r[:, 1] >> 16) & 0xFFFF,
+        "lone_units": r[:, 2] & 0xFFFF,
+        "records": (r[:, 2] >> 16) & 0xFF,
+    }
+
+
+def decode_launch_id(records: np.ndarray) -> dict:
+    """Word 3 of the records of kfmi_search_seeds_trace and
+    kfmi_search_strands_trace, the launch identity: int64 arrays per name in
+    LAUNCH_ID_FIELDS -- the fetch form (8, 7, 4, 1), the code registers (8, 16),
+    the kernel (an index into TRACE_KERNELS), skip_split as the kernel received
+    it, whether the jump-start table in use is folded and its step count."""
+    w = np.asarray(records, dtype=np.uint32).reshape(-1, 4)[:, 3].astype(np.int64)
+    return {
+        "form": w & 0xF,
+        "maxw": 8 * ((w >> 4) & 0xF),
+        "kernel": (w >> 8) & 0xF,
+        "skip_split": (w >> 12) & 0xF,
+        "ftab_folded": (w >> 16) & 1,
+        "ftab_steps": (w >> 24) & 0xFF,
+    }
+
+
+def search_strands_trace(index: Index, reads: np.ndarray, backend: str | None = None, strands: int = STRAND_BOTH):
+    """kfmi_search_strands_trace, one shot: the search search_array(...,
+    strands=) runs (STRAND_REV or STRAND_BOTH) with the traced strand kernels.
+    Returns (intervals uint32 [2 * ns * N], records uint32 [ns * N, 4]);
+    decode_trace names words 0 .. 2, decode_launch_id word 3."""
+    if backend:
+        set_backend(backend)
+    tasks = _strand_count(strands) * reads.shape[0]
+    q = Queries.from_array(reads)
+    r = Results.alloc(tasks)
+    rec = np.zeros((tasks, 4), dtype=np.uint32)
+    try:
+        transfer_to_gpu(index, q, r)
+        _check(load().kfmi_search_strands_trace(index.ptr, q.ptr, r.ptr, int(strands),
+                                                rec.ctypes.data_as(ctypes.c_void_p)), "kfmi_search_strands_trace")
+        transfer_to_cpu(r)
+        return r.array().copy(), rec
+    finally:
+        q.close()
+        r.close()
+
+
+def search_seeds_trace(index: Index, reads: np.ndarray, backend: str | None = None, max_seeds: int = 4,
+                       strands: int = STRAND_FWD):
+    """kfmi_search_seeds_trace, one shot: the search search_seeds_array runs with
+    the traced seed kernels.  Returns (intervals, spans, records): the first two
+    uint32 [ns * N, max_seeds, 2], records uint32 [ns * N, 4]; decode_seed_trace
+    names words 0 .. 2, decode_launch_id word 3."""
+    if backend:
+        set_backend(backend)
+    n, s = reads.shape[0], int(max_seeds)
+    tasks = _strand_count(strands) * n
+    q = Queries.from_array(reads)
+    iv, sp = Results.alloc(max(s, 0) * tasks), Results.alloc(max(s, 0) * tasks)
+    rec = np.zeros((tasks, 4), dtype=np.uint32)
+    try:
+        transfer_to_gpu(index, q, iv)
+        transfer_to_gpu(index, None, sp)
+        _check(load().kfmi_search_seeds_trace(index.ptr, q.ptr, iv.ptr, sp.ptr, s, int(strands),
+                                              rec.ctypes.data_as(ctypes.c_void_p)), "kfmi_search_seeds_trace")
+        transfer_to_cpu(iv)
+        transfer_to_cpu(sp)
+        return iv.array().copy().reshape(tasks, s, 2), sp.array().copy().reshape(tasks, s, 2), rec
     finally:
         q.close()
         iv.close()

@@ -26,6 +26,8 @@ packs first and a skip table is in effect) pick, read from kfmi_kernels.h.
     (2, 128)  task-mid            1          4             1           4
     (2, 192)  task-mid            1          1             1           1
 
+seed_walk_model.expected_form is this table as a function, and
+tests/test_seed_trace.py holds the form of every traced launch to it.
 (2, 192) is not SMALL: its walk is lf_stream whatever the form.  A strand search
 that packs first without a skip table (set_fused(False) under set_skip(0)) runs
 task_kernel<G, 1, 0, SPLIT>, which launch_task sends to form 1 at class 2 on the
