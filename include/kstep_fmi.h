@@ -873,11 +873,31 @@ enum {
   KFMI_TRACE_ID_MAXW_SHIFT = 4, KFMI_TRACE_ID_KERNEL_SHIFT = 8, KFMI_TRACE_ID_SKIP_SPLIT_SHIFT = 12,
   KFMI_TRACE_ID_FTAB_FOLDED = 1u << 16, KFMI_TRACE_ID_FTAB_STEPS_SHIFT = 24,
   KFMI_TRACE_KERNEL_SEED = 0, KFMI_TRACE_KERNEL_SEED_STRANDS = 1, KFMI_TRACE_KERNEL_SEED_WORDS = 2,
-  KFMI_TRACE_KERNEL_TASK_STRANDS = 3, KFMI_TRACE_KERNEL_TASK_WORDS_SKIP = 4
+  KFMI_TRACE_KERNEL_TASK_STRANDS = 3, KFMI_TRACE_KERNEL_TASK_WORDS_SKIP = 4,
+  /* the forward kernels (kfmi_launch_plan alone names them: their records' word 3 is no launch identity): the
+   * fused task kernel plain, with the tables' walk and with the text jump; the plain walk of packed words; the
+   * cooperative kernel */
+  KFMI_TRACE_KERNEL_TASK_FUSED = 5, KFMI_TRACE_KERNEL_TASK_TABLES = 6, KFMI_TRACE_KERNEL_TASK_JUMP = 7,
+  KFMI_TRACE_KERNEL_TASK_WORDS = 8, KFMI_TRACE_KERNEL_COOP = 9
 };
 int32_t kfmi_search_strands_trace(void *index, void *queries, void *results, uint32_t strands, uint32_t *trace);
 int32_t kfmi_search_seeds_trace(void *index, void *queries, void *intervals, void *spans, uint32_t max_seeds,
                                 uint32_t strands, uint32_t *trace);
+/* Test accessor (host only, no device, no handle): the launch plan of one search
+ * from values alone -- the library's own rules (DESIGN.md "launch plan"), the
+ * ones every search form asks.  A search (seeds = 0) or seed search (seeds = 1)
+ * of `strands` on the backend of that name over a K = k, d index in table-size class cls (1, 2,
+ * 4) with reads of m bases; ascii: the ASCII rows are on the device (0: packed by
+ * the host); fused, skip, jump: the fused knob, and whether the skip table and
+ * the text jump are in effect; traced: the traced twin of the call.  Returns the
+ * code the call is refused with, or 0 and out[0 .. 4] = the fetch form (0 for
+ * the cooperative kernel), maxw, words_maxw, the pack launch before the kernel
+ * (0 none, 1 the forward pack, 2 the strand pack from ASCII, 3 from words) and
+ * the kernel, KFMI_TRACE_KERNEL_*.  KFMI_E_BAD_ARGUMENT for a geometry no kernel
+ * is built for. */
+int32_t kfmi_launch_plan(const char *backend, uint32_t k, uint32_t d, uint32_t cls, uint32_t m, uint32_t seeds,
+                         uint32_t strands, uint32_t ascii, uint32_t fused, uint32_t skip, uint32_t jump,
+                         uint32_t traced, int32_t *out);
 
 /* Diagnostic (not in the reference): replays the line requests a
  * task-mid / coop-mid search of `queries` makes (MID128 layout, K = 2, d = 64,

@@ -1293,6 +1293,49 @@ struct SearchLaunch {
   uint4* trace;
 };
 
+/* The geometries that have seed, traced and traced strand kernels, and the text
+ * jump: the plain-counter layouts at K <= 2 (KFMI_FOR_LANE_GEOMETRIES below). */
+constexpr bool lane_kernels(uint32_t K, int lay) { return (lay == LAY_INTER || lay == LAY_MID) && K >= 1 && K <= 2; }
+
+/* The fetch form (the SPLIT template value, fetch_ends_split) of the task, strand
+ * and seed kernels of geometry G: `want` is the table-size class (IdxArgs::split,
+ * split_for: 1, 2 or 4) and mw the MAXW of the kernel that will run, 0 for the
+ * plain walk of packed words.  The split only exists for the one-line-per-block
+ * path (SMALL: d <= 128 at K = 2): the asm fetch in one group below 2 GB and in
+ * two groups above (X4 geometries); else the C++ fetch, in four groups at class
+ * 4 and, for the 8-register kernels, at class 2.  The one rule: launch_task,
+ * launch_seeds and the plan's test accessor (kfmi_launch_plan) all ask here. */
+template <class G>
+constexpr int fetch_form(uint32_t want, int mw)
+{
+  if constexpr (G::SMALL && X4<G>::OK) return want == 1 ? 8 : 7;
+  else if constexpr (G::SMALL) return (want == 4 || (want == 2 && mw == 8)) ? 4 : 1;
+  else return 1;
+}
+
+/* the statement with the constant NAME = V in scope (variadic: a launch arrives expanded, commas and all) */
+#define KFMI_WITH_CONST(NAME, V, ...) \
+  {                                   \
+    constexpr int NAME = V;           \
+    __VA_ARGS__;                      \
+  }
+/* CALL with FORM = fetch_form<G>(WANT, MW) as a constant; under if constexpr, so
+ * that each geometry gets only the forms it can be launched with. */
+#define KFMI_WITH_FETCH_FORM(G, WANT, MW, CALL)                                                 \
+  do {                                                                                          \
+    [[maybe_unused]] const int form_ = fetch_form<G>(WANT, MW);                                 \
+    if constexpr (G::SMALL && X4<G>::OK) {                                                      \
+      if (form_ == 8) KFMI_WITH_CONST(FORM, 8, CALL) else KFMI_WITH_CONST(FORM, 7, CALL)        \
+    } else if constexpr (G::SMALL) {                                                            \
+      if (form_ == 4) KFMI_WITH_CONST(FORM, 4, CALL) else KFMI_WITH_CONST(FORM, 1, CALL)        \
+    } else KFMI_WITH_CONST(FORM, 1, CALL)                                                       \
+  } while (0)
+/* LAUNCH with MAXW = 8 or 16 as a constant, by the run-time register count MW */
+#define KFMI_WITH_MAXW(MW, LAUNCH)                                                              \
+  do {                                                                                          \
+    if ((MW) == 8) KFMI_WITH_CONST(MAXW, 8, LAUNCH) else KFMI_WITH_CONST(MAXW, 16, LAUNCH)      \
+  } while (0)
+
 /* TR = Trace (kfmi_search_trace, trace_one below): the same choices with the
  * traced kernels, which exist for what the text jump serves -- the fused
  * forward walk on the plain layouts at K <= 2; there a search without any table
@@ -1303,103 +1346,71 @@ struct SearchLaunch {
 template <class G, int SPLIT, class TR = NoTrace>
 static void launch_task_split(const SearchLaunch& a)
 {
-  constexpr bool TRACED = G::K <= 2 && (G::LAY == LAY_INTER || G::LAY == LAY_MID);
-  static_assert(!TR::ON || TRACED, "walk trace: fused forward task kernels, plain layouts, K <= 2");
+  static_assert(!TR::ON || lane_kernels(G::K, G::LAY), "walk trace: fused forward task kernels, plain layouts, K <= 2");
   const typename TR::Out tr = TR::from(a.trace);
+  const dim3 grid((uint32_t) ((a.num + 255) / 256)), block(256);
   if (a.maxw) {
     const size_t lds = 4 * (size_t) stage_slot_bytes(a.m);
+    /* the walk with the tables, and the strand staging; LDS: the staging, then 64 x maxw code words per wave */
+    const size_t lds_skip = std::max(lds, (size_t) 4 * 64 * 4 * (size_t) a.maxw);
     if constexpr (G::K <= 2 && (!TR::ON || TR::STRANDS)) {
       if (a.strands) {   /* strand-aware staging, then the fused kernel's own walk */
         const uint64_t tblocks = ((a.strands == 3u ? 2u : 1u) * a.num + 255) / 256;
-        const size_t lds_str = std::max(lds, (size_t) 4 * 64 * 4 * (size_t) a.maxw);
-        if (a.maxw == 8)
-          hipLaunchKernelGGL((task_strands_kernel<G, 8, SPLIT, TR>), dim3((uint32_t) tblocks), dim3(256), lds_str, a.st,
-                             a.ix, a.ascii, a.m, a.num, a.steps, a.strands, a.res, tr);
-        else
-          hipLaunchKernelGGL((task_strands_kernel<G, 16, SPLIT, TR>), dim3((uint32_t) tblocks), dim3(256), lds_str, a.st,
-                             a.ix, a.ascii, a.m, a.num, a.steps, a.strands, a.res, tr);
+        KFMI_WITH_MAXW(a.maxw, hipLaunchKernelGGL((task_strands_kernel<G, MAXW, SPLIT, TR>), dim3((uint32_t) tblocks), block,
+                                                  lds_skip, a.st, a.ix, a.ascii, a.m, a.num, a.steps, a.strands, a.res, tr));
         return;
       }
     }
     if constexpr (!TR::STRANDS) {   /* that policy has the strand kernels only (the caller refused the rest) */
-      const uint64_t blocks = (a.num + 255) / 256;
       if constexpr (G::K <= 2) {
-        if (TR::ON || a.ix.skip || a.ix.jsa) {   /* the walk with the tables; LDS: the staging, then 64 x maxw code words per wave */
-          const size_t lds_skip = std::max(lds, (size_t) 4 * 64 * 4 * (size_t) a.maxw);
+        if (TR::ON || a.ix.skip || a.ix.jsa) {
           if constexpr (G::LAY == LAY_INTER || G::LAY == LAY_MID) {
             if (a.ix.jsa) {   /* with the text jump (DESIGN.md 5a'') */
               IdxArgs ix = a.ix;
               if ((ix.jump_split & JUMP_LINES_GROUPED) && a.m > JUMP_LINES_GROUPED_MAX_M)
                 ix.jump_split &= ~(JUMP_LINES | JUMP_LINES_GROUPED);   /* long reads: the flat tables' form is faster */
-              if (a.maxw == 8)
-                hipLaunchKernelGGL((task_kernel<G, 1, 8, SPLIT, true, true, TR>), dim3((uint32_t) blocks), dim3(256),
-                                   lds_skip, a.st, ix, a.qp, a.ascii, a.m, a.num, a.steps, a.nwords, a.res, tr);
-              else
-                hipLaunchKernelGGL((task_kernel<G, 1, 16, SPLIT, true, true, TR>), dim3((uint32_t) blocks), dim3(256),
-                                   lds_skip, a.st, ix, a.qp, a.ascii, a.m, a.num, a.steps, a.nwords, a.res, tr);
+              KFMI_WITH_MAXW(a.maxw, hipLaunchKernelGGL((task_kernel<G, 1, MAXW, SPLIT, true, true, TR>), grid, block, lds_skip,
+                                                        a.st, ix, a.qp, a.ascii, a.m, a.num, a.steps, a.nwords, a.res, tr));
               return;
             }
           }
-          if (a.maxw == 8)
-            hipLaunchKernelGGL((task_kernel<G, 1, 8, SPLIT, true, false, TR>), dim3((uint32_t) blocks), dim3(256), lds_skip,
-                               a.st, a.ix, a.qp, a.ascii, a.m, a.num, a.steps, a.nwords, a.res, tr);
-          else
-            hipLaunchKernelGGL((task_kernel<G, 1, 16, SPLIT, true, false, TR>), dim3((uint32_t) blocks), dim3(256), lds_skip,
-                               a.st, a.ix, a.qp, a.ascii, a.m, a.num, a.steps, a.nwords, a.res, tr);
+          KFMI_WITH_MAXW(a.maxw, hipLaunchKernelGGL((task_kernel<G, 1, MAXW, SPLIT, true, false, TR>), grid, block, lds_skip,
+                                                    a.st, a.ix, a.qp, a.ascii, a.m, a.num, a.steps, a.nwords, a.res, tr));
           return;
         }
       }
-      if constexpr (!TR::ON) {
-        if (a.maxw == 8)
-          hipLaunchKernelGGL((task_kernel<G, 1, 8, SPLIT>), dim3((uint32_t) blocks), dim3(256), lds, a.st, a.ix, a.qp,
-                             a.ascii, a.m, a.num, a.steps, a.nwords, a.res, tr);
-        else
-          hipLaunchKernelGGL((task_kernel<G, 1, 16, SPLIT>), dim3((uint32_t) blocks), dim3(256), lds, a.st, a.ix, a.qp,
-                             a.ascii, a.m, a.num, a.steps, a.nwords, a.res, tr);
-      }
+      if constexpr (!TR::ON)
+        KFMI_WITH_MAXW(a.maxw, hipLaunchKernelGGL((task_kernel<G, 1, MAXW, SPLIT>), grid, block, lds, a.st, a.ix, a.qp,
+                                                  a.ascii, a.m, a.num, a.steps, a.nwords, a.res, tr));
     }
   } else if constexpr (!TR::ON || TR::STRANDS) {
-    const uint64_t blocks = (a.num + 255) / 256;
     if constexpr (G::K <= 2) {
       if (a.ix.skip && a.words_maxw) {   /* strand searches: the skip-table walk on packed words */
         const size_t lds_skip = (size_t) 4 * 64 * 4 * (size_t) a.words_maxw;
-        if (a.words_maxw == 8)
-          hipLaunchKernelGGL((task_words_skip_kernel<G, 8, SPLIT, TR>), dim3((uint32_t) blocks), dim3(256), lds_skip,
-                             a.st, a.ix, a.qp, a.num, a.steps, a.nwords, a.res, tr);
-        else
-          hipLaunchKernelGGL((task_words_skip_kernel<G, 16, SPLIT, TR>), dim3((uint32_t) blocks), dim3(256), lds_skip,
-                             a.st, a.ix, a.qp, a.num, a.steps, a.nwords, a.res, tr);
+        KFMI_WITH_MAXW(a.words_maxw, hipLaunchKernelGGL((task_words_skip_kernel<G, MAXW, SPLIT, TR>), grid, block, lds_skip,
+                                                        a.st, a.ix, a.qp, a.num, a.steps, a.nwords, a.res, tr));
         return;
       }
     }
     if constexpr (!TR::ON)
-      hipLaunchKernelGGL((task_kernel<G, 1, 0, SPLIT>), dim3((uint32_t) blocks), dim3(256), 0, a.st, a.ix, a.qp,
-                         a.ascii, a.m, a.num, a.steps, a.nwords, a.res, tr);
+      hipLaunchKernelGGL((task_kernel<G, 1, 0, SPLIT>), grid, block, 0, a.st, a.ix, a.qp, a.ascii, a.m, a.num, a.steps,
+                         a.nwords, a.res, tr);
   }
 }
 
+/* mw: the words-skip kernel takes the fused skip kernel's form; the plain walk
+ * of words keeps its own. */
 template <class G, class TR = NoTrace>
 static hipError_t launch_task(const SearchLaunch& a)
 {
-  /* the split only exists for the one-line-per-block path (d <= 128 at K=2);
-   * one fetch form per (geometry, table size class): the asm fetch in one group
-   * below 2 GB, two groups above (X4 geometries); else the C++ fetch, in four
-   * groups where split_for asks for them */
-  if constexpr (G::SMALL) {
-    const uint32_t want = a.ix.split;
-    if constexpr (X4<G>::OK) {
-      if (want == 1) launch_task_split<G, 8, TR>(a);
-      else launch_task_split<G, 7, TR>(a);
-      return hipGetLastError();
-    }
-    /* the words-skip kernel takes the fused skip kernel's form; the plain walk of words keeps its own */
-    const int mw = a.maxw ? a.maxw : (a.ix.skip ? a.words_maxw : 0);
-    if (want == 4 || (want == 2 && mw == 8)) {
-      launch_task_split<G, 4, TR>(a);
-      return hipGetLastError();
-    }
+  const int mw = a.maxw ? a.maxw : (a.ix.skip ? a.words_maxw : 0);
+  KFMI_WITH_FETCH_FORM(G, a.ix.split, mw, (launch_task_split<G, FORM, TR>(a)));
+  if constexpr (G::SMALL && X4<G>::OK) {
+    /* the C++ fetch forms of the asm geometries: never launched; named so that the
+     * units hold the kernels they held before the rule moved to fetch_form */
+    (void) &launch_task_split<G, 4, TR>;
+    (void) &launch_task_split<G, 1, TR>;
   }
-  launch_task_split<G, 1, TR>(a);
   return hipGetLastError();
 }
 
@@ -1410,49 +1421,34 @@ template <class G, int SPLIT, class TR = NoTrace>
 static void launch_seeds_split(const SearchLaunch& a)
 {
   const typename TR::Out tr = TR::from(a.trace);
-#define KFMI_SEED_MAXW(MW, KERNEL, GRID, LDS, ...)                                                           \
-  do {                                                                                                       \
-    if ((MW) == 8)                                                                                           \
-      hipLaunchKernelGGL((KERNEL<G, 8, SPLIT, TR>), dim3((uint32_t) (GRID)), dim3(256), LDS, a.st, __VA_ARGS__, tr); \
-    else                                                                                                     \
-      hipLaunchKernelGGL((KERNEL<G, 16, SPLIT, TR>), dim3((uint32_t) (GRID)), dim3(256), LDS, a.st, __VA_ARGS__, tr); \
-  } while (0)
+  const dim3 grid((uint32_t) ((a.num + 255) / 256)), block(256);
   if (a.maxw) {   /* LDS: the staging, then 64 x maxw code words per wave */
     const size_t lds = std::max((size_t) 4 * stage_slot_bytes(a.m), (size_t) 4 * 64 * 4 * (size_t) a.maxw);
     if (a.strands) {
       const uint64_t tblocks = ((a.strands == 3u ? 2u : 1u) * a.num + 255) / 256;
-      KFMI_SEED_MAXW(a.maxw, seed_strands_kernel, tblocks, lds, a.ix, a.ascii, a.m, a.num, a.steps, a.strands,
-                     a.max_seeds, a.res, a.spans);
+      KFMI_WITH_MAXW(a.maxw, hipLaunchKernelGGL((seed_strands_kernel<G, MAXW, SPLIT, TR>), dim3((uint32_t) tblocks), block, lds,
+                                                a.st, a.ix, a.ascii, a.m, a.num, a.steps, a.strands, a.max_seeds, a.res,
+                                                a.spans, tr));
     } else {
-      KFMI_SEED_MAXW(a.maxw, seed_kernel, (a.num + 255) / 256, lds, a.ix, a.ascii, a.m, a.num, a.steps, a.max_seeds,
-                     a.res, a.spans);
+      KFMI_WITH_MAXW(a.maxw, hipLaunchKernelGGL((seed_kernel<G, MAXW, SPLIT, TR>), grid, block, lds, a.st, a.ix, a.ascii, a.m,
+                                                a.num, a.steps, a.max_seeds, a.res, a.spans, tr));
     }
   } else {
     const size_t lds = (size_t) 4 * 64 * 4 * (size_t) a.words_maxw;
-    KFMI_SEED_MAXW(a.words_maxw, seed_words_kernel, (a.num + 255) / 256, lds, a.ix, a.qp, a.m, a.num, a.steps,
-                   a.nwords, a.max_seeds, a.res, a.spans);
+    KFMI_WITH_MAXW(a.words_maxw, hipLaunchKernelGGL((seed_words_kernel<G, MAXW, SPLIT, TR>), grid, block, lds, a.st, a.ix,
+                                                    a.qp, a.m, a.num, a.steps, a.nwords, a.max_seeds, a.res, a.spans, tr));
   }
-#undef KFMI_SEED_MAXW
 }
 
-/* The fetch form is launch_task's for the same geometry and table size class.
+/* The fetch form is fetch_form's for the kernel's registers, as for launch_task.
  * TR = Trace (kfmi_search_seeds_trace): the same choices with the traced kernels. */
 template <class G, class TR = NoTrace>
 static hipError_t launch_seeds(const SearchLaunch& a)
 {
-  if constexpr (G::K <= 2 && (G::LAY == LAY_INTER || G::LAY == LAY_MID)) {
+  if constexpr (lane_kernels(G::K, G::LAY)) {
     const int mw = a.maxw ? a.maxw : a.words_maxw;
     if (mw != 8 && mw != 16) return hipErrorInvalidValue;
-    const uint32_t want = a.ix.split;
-    if constexpr (G::SMALL && X4<G>::OK) {   /* each geometry gets only the forms it can be launched with */
-      if (want == 1) launch_seeds_split<G, 8, TR>(a);
-      else launch_seeds_split<G, 7, TR>(a);
-    } else if constexpr (G::SMALL) {
-      if (want == 4 || (want == 2 && mw == 8)) launch_seeds_split<G, 4, TR>(a);
-      else launch_seeds_split<G, 1, TR>(a);
-    } else {
-      launch_seeds_split<G, 1, TR>(a);
-    }
+    KFMI_WITH_FETCH_FORM(G, a.ix.split, mw, (launch_seeds_split<G, FORM, TR>(a)));
     return hipGetLastError();
   } else {
     return hipErrorInvalidValue;
@@ -1478,6 +1474,14 @@ static hipError_t launch_count(const SearchLaunch& a, unsigned long long* d_tota
 /* K in {1,2}; d in {32,64,128,192,256,448,960} */
 #define KFMI_FOR_NB(X, K, LAY) \
   X(K, 1, LAY) X(K, 2, LAY) X(K, 4, LAY) X(K, 6, LAY) X(K, 8, LAY) X(K, 14, LAY) X(K, 30, LAY)
+/* the geometries of lane_kernels(): seeds_one, trace_one, strands_trace_one, seeds_trace_one */
+#define KFMI_FOR_LANE_GEOMETRIES(X) \
+  KFMI_FOR_NB(X, 1, LAY_INTER) KFMI_FOR_NB(X, 2, LAY_INTER) KFMI_FOR_NB(X, 1, LAY_MID) KFMI_FOR_NB(X, 2, LAY_MID)
+/* every geometry dispatch_one is instantiated for (kfmi_inst_*.hip) */
+#define KFMI_FOR_GEOMETRIES(X)                                                                             \
+  KFMI_FOR_NB(X, 1, LAY_INTER) KFMI_FOR_NB(X, 2, LAY_INTER) KFMI_FOR_NB(X, 1, LAY_AC) KFMI_FOR_NB(X, 2, LAY_AC) \
+  KFMI_FOR_NB(X, 1, LAY_MID) KFMI_FOR_NB(X, 2, LAY_MID) KFMI_FOR_NB(X, 1, LAY_MIDAC) KFMI_FOR_NB(X, 2, LAY_MIDAC) \
+  X(4, 2, LAY_GRP) X(3, 2, LAY_GRP)
 
 
 /* Locate: enough lanes to fill every CU (8 workgroups of 256 per CU), each

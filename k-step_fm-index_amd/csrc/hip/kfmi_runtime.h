@@ -5,12 +5,16 @@
  * tables and their settings), kfmi_group.hip (device groups), kfmi_locate.hip
  * (locate), kfmi_strands.hip / kfmi_seeds.hip / kfmi_verify.hip (strand and
  * seed searches) and kfmi_stream.hip (streamed search, host worker pool).
+ * Where a search's code words come from -- maxw, words_maxw, strands, the pack
+ * launch -- is decided in one place, kfmi_plan.h; plan_for / plan_launch /
+ * plan_pack below are how every search form uses it.
  */
 #ifndef KFMI_RUNTIME_H_
 #define KFMI_RUNTIME_H_
 
 #include <hip/hip_runtime.h>
 #include <atomic>
+#include <initializer_list>
 #include <stdint.h>
 #include <stdio.h>
 #include <mutex>
@@ -20,6 +24,7 @@
 #include "../kfmi_internal.h"
 #include "kfmi_devguard.h"
 #include "kfmi_kernels.h"
+#include "kfmi_plan.h"
 
 #define HIP_OK(x)                                                                   \
   do {                                                                              \
@@ -159,7 +164,9 @@ extern thread_local double t_ms[3];   /* kfmi_last_timing: total, pack, lf (ms) 
 /* backends and kernel dispatch (kfmi_search.hip) */
 bool is_coop(int backend);
 int backend_for(uint32_t K);   /* the selected backend, or coop-grp for K = 4 under the implicit default */
-int fused_maxw(int backend, uint32_t bases);   /* bases = K * steps of the batch */
+bool fused_on();               /* the fused knob (KFMI_FUSED, kfmi_set_fused) */
+/* per-lane kernels on the plain-counter layouts at K <= 2: the copies with seed, traced and verify kernels */
+inline bool lane_kernels(const kfmi_dev_index* di) { return !is_coop(di->backend) && lane_kernels(di->K, di->layout); }
 int32_t check_lf_walks(kfmi_dev_index* di, hipStream_t st);   /* sets di->lf_perm (kfmi_search.hip) */
 hipError_t dispatch(Op op, uint32_t K, uint32_t nb, int lay, const SearchLaunch& a,
                     unsigned long long* d_total = nullptr);
@@ -219,10 +226,46 @@ void free_dev_index(kfmi_dev_index* di);
 void free_dev_queries(kfmi_dev_queries* dq);
 hipError_t h2d(void* dst, const void* src, uint64_t bytes, hipStream_t st);
 
-/* one device batch: queue pack + LF bracketed by ev[0..2], then wait (kfmi_search.hip) */
-/* trace: null, or num records on the device (kfmi_search_trace: the traced kernels, Op::Trace) */
+/* The launch plan (kfmi_plan.h) of one search of dq's reads on di, and what
+ * every search form does with it (kfmi_search.hip).  ascii: the batch's or
+ * chunk's ASCII rows are on the device; skip: ix.skip != nullptr. */
+LaunchPlan plan_for(const kfmi_dev_index* di, const kfmi_dev_queries* dq, bool ascii, bool seeds, uint32_t strands,
+                    bool skip, bool traced = false, int fused = -1 /* the knob; 0 / 1 for the counts and the accessor */);
+/* the plan's launch, value-initialised: every field a search kernel reads but a seed search's spans and max_seeds */
+SearchLaunch plan_launch(const LaunchPlan& p, hipStream_t st, const IdxArgs& ix, const kfmi_dev_queries* dq,
+                         uint32_t* res, uint4* trace = nullptr);
+hipError_t plan_pack(const LaunchPlan& p, const kfmi_dev_queries* dq, uint32_t strands, hipStream_t st);
+
+/* The checks every entry point on resident single-device handles makes, in this
+ * order: group handles (KFMI_E_NOT_IMPLEMENTED; kfmi_search sends them to
+ * group_search first), missing device copies, `need` for the callers that refuse
+ * these before the last one -- NEED_LANE_KERNELS, NEED_ASCII -- and results on
+ * another device than the index. */
+enum { NEED_LANE_KERNELS = 1, NEED_ASCII = 2 };
+bool any_group(const kfmi_fmi_t* f, const kfmi_qrys_t* q, std::initializer_list<const kfmi_res_t*> rs);
+int32_t resident_single(const kfmi_fmi_t* f, const kfmi_qrys_t* q, std::initializer_list<const kfmi_res_t*> rs,
+                        unsigned need = 0);
+
+/* one device batch: queue pack + kernel bracketed by ev[0..2], then wait (kfmi_search.hip).  SearchWhat: the strand
+ * mode; a seed search's spans and max_seeds (d_res holds its intervals); null, or the device records of the traced
+ * twin, one per read or task; the context whose lock strand_reserve takes (every form but the forward search) */
+struct SearchWhat {
+  uint32_t strands = KFMI_STRAND_FWD;
+  uint32_t* spans = nullptr;
+  uint32_t max_seeds = 0;
+  uint4* trace = nullptr;
+  DevCtx* ctx = nullptr;
+};
 int32_t search_enqueue(kfmi_dev_index* di, kfmi_dev_queries* dq, uint32_t* d_res, hipStream_t st, hipEvent_t* ev,
-                       const TableWants& want, uint4* trace = nullptr);
+                       const TableWants& want, const SearchWhat& w = SearchWhat{});
+/* the launches of the seed kernels and of the traced strand kernels (kfmi_seeds.hip, kfmi_strands.hip) */
+hipError_t dispatch_seeds(uint32_t K, uint32_t nb, int lay, const SearchLaunch& a);
+hipError_t dispatch_strands_trace(uint32_t K, uint32_t nb, int lay, const SearchLaunch& a);
+/* One resident search of f->dev and q->dev on the calling thread's lane: enqueue and finish (timings in t_ms).  The
+ * traced twin (`trace`: 16 bytes per task) owns its device records here: allocated for max(tasks, 1) before anything
+ * is queued (KFMI_E_DEVICE_ALLOC), copied out after a successful finish (KFMI_E_KERNEL), always freed. */
+int32_t search_run(kfmi_fmi_t* f, kfmi_qrys_t* q, uint32_t* d_res, const TableWants& want, SearchWhat w = SearchWhat{},
+                   uint32_t* trace = nullptr, uint64_t tasks = 0);
 int32_t search_finish(hipStream_t st, hipEvent_t* ev, double* ms);
 
 /* strand searches (kfmi_strands.hip): dq->strand_words sized for both strands
@@ -230,9 +273,6 @@ int32_t search_finish(hipStream_t st, hipEvent_t* ev, double* ms);
  * `strands` (REV or BOTH) -- from dq->ascii, or from the forward code words in
  * dq->packed when from_words (or when the device has no ASCII) */
 int32_t strand_reserve(kfmi_dev_queries* dq, uint64_t cq, DevCtx* ctx);
-int strand_words_maxw(uint32_t nwords);   /* SearchLaunch::words_maxw of a strand search */
-/* SearchLaunch::maxw of a strand search that packs in the task kernel (task_strands_kernel); 0 = the pack launch */
-int strand_fused_maxw(const kfmi_dev_index* di, bool ascii, uint32_t K, uint32_t steps, uint32_t rem);
 hipError_t launch_strand_pack(const kfmi_dev_queries* dq, uint32_t* out, uint32_t strands, bool from_words,
                               hipStream_t st);
 

@@ -7,7 +7,10 @@
  * kfmi_coop.h / kfmi_locate.h (instantiated in kfmi_inst_*.hip); the tables
  * derived from an uploaded index and their settings in kfmi_tables.hip and
  * kfmi_jump.hip; device groups, locate and streaming in kfmi_group.hip,
- * kfmi_locate.hip and kfmi_stream.hip.
+ * kfmi_locate.hip and kfmi_stream.hip.  Where a search's code words come
+ * from and which pack launch precedes its kernel is the launch plan's answer
+ * (kfmi_plan.h; plan_for / plan_launch / plan_pack here), the kernel's fetch
+ * form fetch_form's (kfmi_kernels.h); kfmi_launch_plan shows both to a test.
  *
  * Semantics: results are bit-identical to the reference CPU searchers
  * (fmIndexCPUBaseline.c:157-292 for task/coop/mid, -AltCounters.c:145-310
@@ -18,6 +21,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 #include <atomic>
 #include <mutex>
 #include <new>
@@ -408,90 +412,40 @@ __global__ __launch_bounds__(256) void build_grp_kernel(const uint32_t* __restri
   for (int i = GI::BMW + GG::NCG; i < GG::EW; ++i) dst[i] = 0;
 }
 
-/* Code registers the task kernel needs to pack a query itself (0: use the
- * pack kernel).  KFMI_FUSED=0 / kfmi_set_fused(0) forces the separate pack launch. */
-/* Fused packing keeps 16 bases per register word (MAXW words): 8 words up to
- * 128 K-step bases, 16 up to 256, else the pack kernel. */
-int fused_maxw(int backend, uint32_t bases)
-{
-  (void) backend;   /* task and coop kernels both pack in-kernel (m <= 256 fits either's LDS staging) */
-  if (!knob_once(g_fused, fused_from_env)) return 0;
-  return bases <= 128 ? 8 : (bases <= 256 ? 16 : 0);
-}
-
-static bool nb_supported(uint32_t nb)
-{
-  return nb == 1 || nb == 2 || nb == 4 || nb == 6 || nb == 8 || nb == 14 || nb == 30;
-}
+/* KFMI_FUSED=0 / kfmi_set_fused(0) forces the separate pack launch (fused_maxw, kfmi_plan.h) */
+bool fused_on() { return knob_once(g_fused, fused_from_env) != 0; }
 
 /* dispatch_one<K, NB, LAY> is compiled in kfmi_inst_*.hip (one unit per K and
- * layout, built in parallel). */
-KFMI_FOR_NB(KFMI_EXTERN, 1, LAY_INTER)
-KFMI_FOR_NB(KFMI_EXTERN, 2, LAY_INTER)
-KFMI_FOR_NB(KFMI_EXTERN, 1, LAY_AC)
-KFMI_FOR_NB(KFMI_EXTERN, 2, LAY_AC)
-KFMI_FOR_NB(KFMI_EXTERN, 1, LAY_MID)
-KFMI_FOR_NB(KFMI_EXTERN, 2, LAY_MID)
-KFMI_FOR_NB(KFMI_EXTERN, 1, LAY_MIDAC)
-KFMI_FOR_NB(KFMI_EXTERN, 2, LAY_MIDAC)
-KFMI_EXTERN(4, 2, LAY_GRP)
-KFMI_EXTERN(3, 2, LAY_GRP)
-/* trace_one<K, NB, LAY> (Op::Trace) is compiled in kfmi_inst_trace_*.hip */
-KFMI_FOR_NB(KFMI_TRACE_EXTERN, 1, LAY_INTER)
-KFMI_FOR_NB(KFMI_TRACE_EXTERN, 2, LAY_INTER)
-KFMI_FOR_NB(KFMI_TRACE_EXTERN, 1, LAY_MID)
-KFMI_FOR_NB(KFMI_TRACE_EXTERN, 2, LAY_MID)
+ * layout, built in parallel), trace_one<K, NB, LAY> (Op::Trace) in kfmi_inst_trace_*.hip */
+KFMI_FOR_GEOMETRIES(KFMI_EXTERN)
+KFMI_FOR_LANE_GEOMETRIES(KFMI_TRACE_EXTERN)
 
 hipError_t dispatch(Op op, uint32_t K, uint32_t nb, int lay, const SearchLaunch& a, unsigned long long* d_total)
 {
   if (op == Op::Trace) {   /* the traced task kernels: the geometries that have them */
 #define KFMI_CASE(KK, NBV, LAYV) \
   if (K == KK && nb == NBV && lay == LAYV) return trace_one<KK, NBV, LAYV>(a);
-    KFMI_FOR_NB(KFMI_CASE, 1, LAY_INTER)
-    KFMI_FOR_NB(KFMI_CASE, 2, LAY_INTER)
-    KFMI_FOR_NB(KFMI_CASE, 1, LAY_MID)
-    KFMI_FOR_NB(KFMI_CASE, 2, LAY_MID)
+    KFMI_FOR_LANE_GEOMETRIES(KFMI_CASE)
 #undef KFMI_CASE
     return hipErrorInvalidValue;
   }
 #define KFMI_CASE(KK, NBV, LAYV)                                   \
   if (K == KK && nb == NBV && lay == LAYV) return dispatch_one<KK, NBV, LAYV>(op, a, d_total);
-  KFMI_FOR_NB(KFMI_CASE, 1, LAY_INTER)
-  KFMI_FOR_NB(KFMI_CASE, 2, LAY_INTER)
-  KFMI_FOR_NB(KFMI_CASE, 1, LAY_AC)
-  KFMI_FOR_NB(KFMI_CASE, 2, LAY_AC)
-  KFMI_FOR_NB(KFMI_CASE, 1, LAY_MID)
-  KFMI_FOR_NB(KFMI_CASE, 2, LAY_MID)
-  KFMI_FOR_NB(KFMI_CASE, 1, LAY_MIDAC)
-  KFMI_FOR_NB(KFMI_CASE, 2, LAY_MIDAC)
-  KFMI_CASE(4, 2, LAY_GRP)
-  KFMI_CASE(3, 2, LAY_GRP)
+  KFMI_FOR_GEOMETRIES(KFMI_CASE)
 #undef KFMI_CASE
   return hipErrorInvalidValue;
 }
 
 bool is_coop(int backend);
 
-/* Whether the backend's kernel exists for this geometry (the cooperative
- * kernel needs 16-byte-aligned chunks, CoopCfg::OK). */
+/* Whether the backend's kernel exists for this geometry: one of dispatch's (GRP
+ * for K = 3, 4 with d = 64 only: K <= 2 has the MID128 lines), and for the
+ * cooperative kernel 16-byte-aligned chunks (CoopCfg::OK). */
 static bool geometry_supported(int backend, uint32_t K, uint32_t nb, int lay)
 {
-  if (lay == LAY_GRP) {   /* instantiated for K = 3, 4 with d = 64 (K <= 2 has the MID128 lines) */
-    if ((K != 3 && K != 4) || nb != 2) return false;
-    return !is_coop(backend) || (K == 4 ? CoopCfg<Geo<4, 2, LAY_GRP>>::OK : CoopCfg<Geo<3, 2, LAY_GRP>>::OK);
-  }
-  if (!nb_supported(nb) || (K != 1 && K != 2)) return false;
-  if (!is_coop(backend)) return true;
 #define KFMI_OKC(KK, NBV, LAYV) \
-  if (K == KK && nb == NBV && lay == LAYV) return CoopCfg<Geo<KK, NBV, LAYV>>::OK;
-  KFMI_FOR_NB(KFMI_OKC, 1, LAY_INTER)
-  KFMI_FOR_NB(KFMI_OKC, 2, LAY_INTER)
-  KFMI_FOR_NB(KFMI_OKC, 1, LAY_AC)
-  KFMI_FOR_NB(KFMI_OKC, 2, LAY_AC)
-  KFMI_FOR_NB(KFMI_OKC, 1, LAY_MID)
-  KFMI_FOR_NB(KFMI_OKC, 2, LAY_MID)
-  KFMI_FOR_NB(KFMI_OKC, 1, LAY_MIDAC)
-  KFMI_FOR_NB(KFMI_OKC, 2, LAY_MIDAC)
+  if (K == KK && nb == NBV && lay == LAYV) return !is_coop(backend) || CoopCfg<Geo<KK, NBV, LAYV>>::OK;
+  KFMI_FOR_GEOMETRIES(KFMI_OKC)
 #undef KFMI_OKC
   return false;
 }
@@ -906,7 +860,6 @@ int32_t upload_index(kfmi_fmi_t* f, int backend, int dev, DevCtx* ctx, kfmi_dev_
     return KFMI_SUCCESS;
   }
   if (f->steps < 1 || f->steps > 4) return KFMI_E_BAD_ARGUMENT;   /* GPU kernels: K in {1,2}; 4 on LAY_GRP */
-  if (!nb_supported(f->nbitmaps)) return KFMI_E_BAD_ARGUMENT;
   const int lay = layout_of(backend);
   if (!geometry_supported(backend, f->steps, f->nbitmaps, lay)) return KFMI_E_BAD_ARGUMENT;
   /* rows are u32 on the device: every layout's padding blocks and the
@@ -1706,33 +1659,130 @@ extern "C" int32_t transferCPUtoGPU(void* index, void* queries, void* results)
   return KFMI_SUCCESS;
 }
 
-/* Queues pack (if not fused) + LF of one device batch on `st`, bracketed by
- * ev[0..2]; search_finish waits and reads the timings. */
-int32_t search_enqueue(kfmi_dev_index* di, kfmi_dev_queries* dq, uint32_t* d_res, hipStream_t st,
-                              hipEvent_t* ev, const TableWants& want, uint4* trace)
+LaunchPlan plan_for(const kfmi_dev_index* di, const kfmi_dev_queries* dq, bool ascii, bool seeds, uint32_t strands,
+                    bool skip, bool traced, int fused)
 {
-  if (dq->device != di->device || dq->K != di->K) return KFMI_E_BAD_ARGUMENT;
+  return launch_plan(PlanIn{is_coop(di->backend), di->layout, dq->K, seeds, strands, ascii, dq->steps, dq->nwords, dq->rem,
+                            fused < 0 ? fused_on() : fused != 0, skip, traced});
+}
+
+SearchLaunch plan_launch(const LaunchPlan& p, hipStream_t st, const IdxArgs& ix, const kfmi_dev_queries* dq,
+                         uint32_t* res, uint4* trace)
+{
   SearchLaunch a{};
   a.st = st;
-  a.ix = idx_args(di);
-  const int32_t err = use_tables(di, st, a.ix, want, dq->rem);
-  if (err) return err;
-  a.qp = dq->packed;
+  a.ix = ix;
+  a.qp = p.strand_words ? dq->strand_words : dq->packed;
   a.ascii = dq->ascii;
   a.m = dq->size;
-  a.maxw = dq->ascii ? fused_maxw(di->backend, dq->K * dq->steps) : 0;
-  a.num = dq->num;
+  a.maxw = p.maxw;
+  a.words_maxw = p.words_maxw;
+  a.strands = p.strands;
+  a.num = p.columns * dq->num;
   a.steps = dq->steps;
   a.nwords = dq->nwords;
-  a.res = d_res;
+  a.res = res;
   a.trace = trace;
-  if (trace && (!a.maxw || is_coop(di->backend))) return KFMI_E_NOT_IMPLEMENTED;   /* no traced kernel */
+  return a;
+}
+
+hipError_t plan_pack(const LaunchPlan& p, const kfmi_dev_queries* dq, uint32_t strands, hipStream_t st)
+{
+  if (p.pack == PACK_NONE) return hipSuccess;
+  if (p.pack == PACK_FORWARD) return launch_pack(dq, st);
+  return launch_strand_pack(dq, dq->strand_words, strands, p.pack == PACK_STRANDS_WORDS, st);
+}
+
+bool any_group(const kfmi_fmi_t* f, const kfmi_qrys_t* q, std::initializer_list<const kfmi_res_t*> rs)
+{
+  return f->grp || q->grp || std::any_of(rs.begin(), rs.end(), [](const kfmi_res_t* r) { return r->grp != nullptr; });
+}
+
+int32_t resident_single(const kfmi_fmi_t* f, const kfmi_qrys_t* q, std::initializer_list<const kfmi_res_t*> rs,
+                        unsigned need)
+{
+  /* group_transfer cuts results by their own count, which only kfmi_search's equals the read slices' */
+  if (any_group(f, q, rs)) return KFMI_E_NOT_IMPLEMENTED;
+  bool there = f->dev && q->dev;
+  for (const kfmi_res_t* r : rs) there = there && r->d_results;
+  if (!there) return KFMI_E_NOT_ON_DEVICE;
+  if ((need & NEED_LANE_KERNELS) && !lane_kernels(f->dev)) return KFMI_E_NOT_IMPLEMENTED;
+  if ((need & NEED_ASCII) && !q->dev->ascii) return KFMI_E_NOT_IMPLEMENTED;   /* KFMI_UPLOAD=packed */
+  for (const kfmi_res_t* r : rs)
+    if (r->d_device != f->dev->device) return KFMI_E_BAD_ARGUMENT;   /* handles transferred to different devices */
+  return KFMI_SUCCESS;
+}
+
+/* Test accessor (kstep_fmi.h): launch_plan, fetch_form<G> over dispatch's
+ * geometries, and the kernel launch_task_split / launch_seeds_split / launch_coop
+ * start for that plan, from values alone. */
+extern "C" int32_t kfmi_launch_plan(const char* backend_name, uint32_t k, uint32_t d, uint32_t cls, uint32_t m,
+                                    uint32_t seeds, uint32_t strands, uint32_t ascii, uint32_t fused, uint32_t skip,
+                                    uint32_t jump, uint32_t traced, int32_t* out)
+{
+  const int backend = backend_from_name(backend_name);
+  if (!out || backend < 0 || k < 1 || k > 4 || d % 32 || !m ||
+      (cls != 1 && cls != 2 && cls != 4) || strands < KFMI_STRAND_FWD || strands > KFMI_STRAND_BOTH)
+    return KFMI_E_BAD_ARGUMENT;
+  kfmi_dev_index di;
+  di.backend = backend;
+  di.layout = layout_of(backend);
+  di.K = k;
+  kfmi_dev_queries dq;
+  dq.size = m;
+  query_geometry(&dq, k);
+  if ((seeds || traced) && !lane_kernels(&di)) return KFMI_E_NOT_IMPLEMENTED;   /* the entry points' own refusal */
+  const LaunchPlan p = plan_for(&di, &dq, ascii != 0, seeds != 0, strands, skip != 0, traced != 0, fused != 0);
+  if (p.refusal) return p.refusal;
+  const bool text_jump = jump && lane_kernels(k, di.layout);
+  const bool tables = k <= 2 && (traced || skip || text_jump);
+  /* the MAXW of the kernel that runs, as launch_seeds and launch_task take it */
+  const int mw = p.maxw ? p.maxw : (seeds || skip ? p.words_maxw : 0);
+  int kernel;
+  if (seeds) kernel = !p.maxw ? KFMI_TRACE_KERNEL_SEED_WORDS : (p.strands ? KFMI_TRACE_KERNEL_SEED_STRANDS : KFMI_TRACE_KERNEL_SEED);
+  else if (is_coop(backend)) kernel = KFMI_TRACE_KERNEL_COOP;
+  else if (p.strands) kernel = KFMI_TRACE_KERNEL_TASK_STRANDS;
+  else if (p.maxw) kernel = !tables ? KFMI_TRACE_KERNEL_TASK_FUSED
+                                    : (text_jump ? KFMI_TRACE_KERNEL_TASK_JUMP : KFMI_TRACE_KERNEL_TASK_TABLES);
+  else if (k <= 2 && skip && p.words_maxw) kernel = KFMI_TRACE_KERNEL_TASK_WORDS_SKIP;
+  else kernel = KFMI_TRACE_KERNEL_TASK_WORDS;
+  int form = -1;
+#define KFMI_FORM(KK, NBV, LAYV) \
+  if (k == KK && d == 32 * NBV && di.layout == LAYV) form = fetch_form<Geo<KK, NBV, LAYV>>(cls, mw);
+  KFMI_FOR_GEOMETRIES(KFMI_FORM)
+#undef KFMI_FORM
+  if (form < 0) return KFMI_E_BAD_ARGUMENT;
+  const int32_t plan[5] = {is_coop(backend) ? 0 : form, p.maxw, p.words_maxw, p.pack, kernel};   /* coop: no fetch forms */
+  memcpy(out, plan, sizeof(plan));
+  return KFMI_SUCCESS;
+}
+
+/* Queues one search of `w` on `st`, bracketed by ev[0..2] (pack if the plan names
+ * one, then the kernel); search_finish waits and reads the timings.  Every form
+ * -- forward, strands, seeds, traced or not -- by the same plan (kfmi_plan.h);
+ * what it refuses is refused before anything is queued. */
+int32_t search_enqueue(kfmi_dev_index* di, kfmi_dev_queries* dq, uint32_t* d_res, hipStream_t st, hipEvent_t* ev,
+                       const TableWants& want, const SearchWhat& w)
+{
+  if (dq->device != di->device || dq->K != di->K) return KFMI_E_BAD_ARGUMENT;
+  const bool seeds = w.spans != nullptr, fwd = w.strands == KFMI_STRAND_FWD;
+  IdxArgs ix = idx_args(di);
+  int32_t err = use_tables(di, st, ix, want, dq->rem);
+  if (err) return err;
+  const LaunchPlan p = plan_for(di, dq, dq->ascii != nullptr, seeds, w.strands, ix.skip != nullptr, w.trace != nullptr);
+  if (p.refusal) return p.refusal;
+  if (p.reserve && (err = strand_reserve(dq, dq->num, w.ctx)) != KFMI_SUCCESS) return err;
+  SearchLaunch a = plan_launch(p, st, ix, dq, d_res, w.trace);
+  a.spans = w.spans;
+  a.max_seeds = w.max_seeds;
   HIP_OK(hipEventRecord(ev[0], st));
-  if (!a.maxw) HIP_OK(launch_pack(dq, st));
+  HIP_OK(plan_pack(p, dq, w.strands, st));
   HIP_OK(hipEventRecord(ev[1], st));
-  if (dq->num) {
-    const Op op = trace ? Op::Trace : (is_coop(di->backend) ? Op::Coop : Op::Task);
-    HIP_OK(dispatch(op, di->K, di->nb, di->layout, a));
+  if (dq->num) {   /* the traced kernels are units of their own, like the seed kernels */
+    const Op op = w.trace ? Op::Trace : (is_coop(di->backend) ? Op::Coop : Op::Task);
+    HIP_OK(seeds ? dispatch_seeds(di->K, di->nb, di->layout, a)
+                 : (w.trace && !fwd ? dispatch_strands_trace(di->K, di->nb, di->layout, a)
+                                    : dispatch(op, di->K, di->nb, di->layout, a)));
   }
   HIP_OK(hipEventRecord(ev[2], st));
   return KFMI_SUCCESS;
@@ -1750,6 +1800,25 @@ int32_t search_finish(hipStream_t st, hipEvent_t* ev, double* ms)
   return KFMI_SUCCESS;
 }
 
+int32_t search_run(kfmi_fmi_t* f, kfmi_qrys_t* q, uint32_t* d_res, const TableWants& want, SearchWhat w, uint32_t* trace,
+                   uint64_t tasks)
+{
+  SearchLane l;
+  int32_t err = search_lane(f->dev->device, &l);
+  if (err) return err;
+  if (trace && hipMalloc((void**) &w.trace, 16ull * (tasks ? tasks : 1)) != hipSuccess) {
+    (void) hipGetLastError();
+    return KFMI_E_DEVICE_ALLOC;
+  }
+  w.ctx = l.ctx;
+  err = search_enqueue(f->dev, q->dev, d_res, l.st, l.ev, want, w);
+  if (!err) err = search_finish(l.st, l.ev, t_ms);
+  if (!err && trace && tasks && hipMemcpy(trace, w.trace, 16ull * tasks, hipMemcpyDeviceToHost) != hipSuccess)
+    err = KFMI_E_KERNEL;
+  (void) hipFree(w.trace);
+  return err;
+}
+
 extern "C" int32_t kfmi_search(void* index, void* queries, void* results)
 {
   kfmi_fmi_t* f = (kfmi_fmi_t*) index;
@@ -1759,15 +1828,9 @@ extern "C" int32_t kfmi_search(void* index, void* queries, void* results)
   if (q->num != r->num) return KFMI_E_BAD_ARGUMENT;
   DeviceGuard dg;
   std::shared_lock<RwLock> lk(index_lock(f));
-  if (f->grp || q->grp || r->grp) return group_search(f, q, r);
-  if (!f->dev || !q->dev || !r->d_results) return KFMI_E_NOT_ON_DEVICE;
-  kfmi_dev_index* di = f->dev;
-  if (r->d_device != di->device) return KFMI_E_BAD_ARGUMENT;   /* handles transferred to different devices */
-  SearchLane l;
-  int32_t err = search_lane(di->device, &l);
-  if (!err) err = search_enqueue(di, q->dev, r->d_results, l.st, l.ev, tables_wanted());
-  if (!err) err = search_finish(l.st, l.ev, t_ms);
-  return err;
+  if (any_group(f, q, {r})) return group_search(f, q, r);
+  const int32_t err = resident_single(f, q, {r});
+  return err ? err : search_run(f, q, r->d_results, tables_wanted());
 }
 
 /* kstep_fmi.h: kfmi_search on resident single-device handles with the traced
@@ -1783,27 +1846,15 @@ extern "C" int32_t kfmi_search_trace(void* index, void* queries, void* results, 
   if (q->num != r->num) return KFMI_E_BAD_ARGUMENT;
   DeviceGuard dg;
   std::shared_lock<RwLock> lk(index_lock(f));
-  if (f->grp || q->grp || r->grp) return KFMI_E_NOT_IMPLEMENTED;
-  if (!f->dev || !q->dev || !r->d_results) return KFMI_E_NOT_ON_DEVICE;
+  int32_t err = resident_single(f, q, {r});
+  if (err) return err;
   kfmi_dev_index* di = f->dev;
   kfmi_dev_queries* dq = q->dev;
-  if (r->d_device != di->device) return KFMI_E_BAD_ARGUMENT;
-  if (is_coop(di->backend) || (di->layout != LAY_INTER && di->layout != LAY_MID) || di->K < 1 || di->K > 2)
-    return KFMI_E_NOT_IMPLEMENTED;
-  if (!dq->ascii || !fused_maxw(di->backend, dq->K * dq->steps)) return KFMI_E_NOT_IMPLEMENTED;
-  SearchLane l;
-  int32_t err = search_lane(di->device, &l);
+  if (!lane_kernels(di)) return KFMI_E_NOT_IMPLEMENTED;
+  /* the plan's own refusal (the skip table does not bear on it), before a lane or the records exist */
+  err = plan_for(di, dq, dq->ascii != nullptr, false, KFMI_STRAND_FWD, false, true).refusal;
   if (err) return err;
-  uint4* d_trace = nullptr;
-  if (hipMalloc((void**) &d_trace, 16ull * (q->num ? q->num : 1)) != hipSuccess) {
-    (void) hipGetLastError();
-    return KFMI_E_DEVICE_ALLOC;
-  }
-  err = search_enqueue(di, dq, r->d_results, l.st, l.ev, tables_wanted(), d_trace);
-  if (!err) err = search_finish(l.st, l.ev, t_ms);
-  if (!err && q->num && hipMemcpy(trace, d_trace, 16ull * q->num, hipMemcpyDeviceToHost) != hipSuccess) err = KFMI_E_KERNEL;
-  (void) hipFree(d_trace);
-  return err;
+  return search_run(f, q, r->d_results, tables_wanted(), SearchWhat{}, trace, q->num);
 }
 
 /* interface.h:31: synchronous like the reference (cudaThreadSynchronize,
@@ -1866,25 +1917,18 @@ static int32_t count_on(kfmi_dev_index* di, kfmi_dev_queries* dq, Op op, uint64_
   DevCtx* ctx = nullptr;
   int32_t err = ctx_for(di->device, &ctx);
   if (err) return err;
-  SearchLaunch a{};
-  a.st = ctx->st;
-  a.ix = idx_args(di);
+  IdxArgs ix = idx_args(di);
   if (dq->device != di->device || dq->K != di->K) return KFMI_E_BAD_ARGUMENT;
-  err = use_tables(di, ctx->st, a.ix, TableWants{}, dq->rem);   /* the remainder table alone */
+  err = use_tables(di, ctx->st, ix, TableWants{}, dq->rem);   /* the remainder table alone */
   if (err) return err;
   unsigned long long* d_total = nullptr;
   HIP_OK(hipMalloc((void**) &d_total, 4 * sizeof(unsigned long long)));
-  a.qp = dq->packed;
-  a.ascii = dq->ascii;
-  a.m = dq->size;
-  a.maxw = 0;
-  a.num = dq->num;
-  a.steps = dq->steps;
-  a.nwords = dq->nwords;
-  a.res = nullptr;
+  /* the statistics kernels read packed words: the forward plan with fused packing off */
+  const LaunchPlan p = plan_for(di, dq, dq->ascii != nullptr, false, KFMI_STRAND_FWD, false, false, 0);
+  const SearchLaunch a = plan_launch(p, ctx->st, ix, dq, nullptr);
   unsigned long long total[4] = {0, 0, 0, 0};
   bool ok = hipMemsetAsync(d_total, 0, sizeof(total), ctx->st) == hipSuccess &&
-            launch_pack(dq, ctx->st) == hipSuccess &&
+            plan_pack(p, dq, KFMI_STRAND_FWD, ctx->st) == hipSuccess &&
             (dq->num == 0 || dispatch(op, di->K, di->nb, di->layout, a, d_total) == hipSuccess) &&
             hipMemcpyAsync(total, d_total, sizeof(total), hipMemcpyDeviceToHost, ctx->st) == hipSuccess &&
             hipStreamSynchronize(ctx->st) == hipSuccess;

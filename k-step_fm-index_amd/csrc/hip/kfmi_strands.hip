@@ -6,11 +6,11 @@
  *
  * A search of ns strands runs ns * num tasks: in BOTH, task t is read t >> 1
  * on strand t & 1 and its interval goes to res + 2t, so every slice of reads
- * is a contiguous slice of results.  The task backends at K <= 2 pack either
- * strand inside the search kernel (task_strands_kernel, kfmi_kernels.h: reads
- * of up to 256 bases, m % K == 0).  Everything else runs the forward LF kernels
- * on ns * num columns of code words; only the words differ.  Three
- * kernels write those task columns on the device:
+ * is a contiguous slice of results.  Where the launch plan (kfmi_plan.h) says
+ * so, either strand is packed inside the search kernel (task_strands_kernel,
+ * kfmi_kernels.h).  Everything else runs the forward LF kernels on ns * num
+ * columns of code words; only the words differ.  Three kernels write those
+ * task columns on the device:
  *   pack_strands_rows_kernel  from the ASCII reads, whole rows in registers
  *                             (m <= 256, m % K == 0, 16 bases per word)
  *   pack_strands_kernel       from the ASCII reads, any K and m (a mirrored
@@ -32,19 +32,13 @@
 namespace kfmi {
 
 /* strands_trace_one<K, NB, LAY> is compiled in kfmi_inst_trace_seeds_*.hip */
-KFMI_FOR_NB(KFMI_SEEDS_TRACE_EXTERN, 1, LAY_INTER)
-KFMI_FOR_NB(KFMI_SEEDS_TRACE_EXTERN, 2, LAY_INTER)
-KFMI_FOR_NB(KFMI_SEEDS_TRACE_EXTERN, 1, LAY_MID)
-KFMI_FOR_NB(KFMI_SEEDS_TRACE_EXTERN, 2, LAY_MID)
+KFMI_FOR_LANE_GEOMETRIES(KFMI_SEEDS_TRACE_EXTERN)
 
-static hipError_t dispatch_strands_trace(uint32_t K, uint32_t nb, int lay, const SearchLaunch& a)
+hipError_t dispatch_strands_trace(uint32_t K, uint32_t nb, int lay, const SearchLaunch& a)
 {
 #define KFMI_CASE(KK, NBV, LAYV) \
   if (K == KK && nb == NBV && lay == LAYV) return strands_trace_one<KK, NBV, LAYV>(a);
-  KFMI_FOR_NB(KFMI_CASE, 1, LAY_INTER)
-  KFMI_FOR_NB(KFMI_CASE, 2, LAY_INTER)
-  KFMI_FOR_NB(KFMI_CASE, 1, LAY_MID)
-  KFMI_FOR_NB(KFMI_CASE, 2, LAY_MID)
+  KFMI_FOR_LANE_GEOMETRIES(KFMI_CASE)
 #undef KFMI_CASE
   return hipErrorInvalidValue;
 }
@@ -284,70 +278,6 @@ int32_t strand_reserve(kfmi_dev_queries* dq, uint64_t cq, DevCtx* ctx)
   return KFMI_SUCCESS;
 }
 
-/* Registers of code words per task for the skip-table walk on packed words
- * (task_words_skip_kernel): 8 or 16 as for fused packing, 0 = longer reads, the
- * plain walk. */
-int strand_words_maxw(uint32_t nwords) { return nwords <= 8 ? 8 : (nwords <= 16 ? 16 : 0); }
-
-/* Code registers of the fused strand kernel (task_strands_kernel) for a batch,
- * 0 = the pack launch: the task backends at K <= 2 with the ASCII reads on the
- * device, m % K == 0 and fused packing on (the forward search's own rule for
- * 8 / 16 words). */
-int strand_fused_maxw(const kfmi_dev_index* di, bool ascii, uint32_t K, uint32_t steps, uint32_t rem)
-{
-  if (!ascii || rem || K > 2 || is_coop(di->backend) || di->layout == LAY_GRP) return 0;
-  return fused_maxw(di->backend, K * steps);
-}
-
-/* search_enqueue for strands != FWD.  Fused (strand_fused_maxw): one launch,
- * the staging derives either strand's code words from the ASCII rows and the
- * walk is the fused kernel's.  Else the strand pack, then the backend's LF
- * kernel on the ns * num task columns (codes from words: MAXW == 0, so the
- * forward kernels run as they are; with the skip table in effect the task
- * backends walk the words with it, task_words_skip_kernel).  trace: null, or
- * one record per task for the traced strand kernels (kfmi_search_strands_trace,
- * whose caller has refused the backends that have none); the plain walk of
- * packed words has no traced form and is refused here, before anything is
- * queued. */
-static int32_t strands_enqueue(kfmi_dev_index* di, kfmi_dev_queries* dq, uint32_t* d_res, hipStream_t st,
-                               hipEvent_t* ev, const TableWants& want, uint32_t strands, DevCtx* ctx,
-                               uint4* trace = nullptr)
-{
-  if (dq->device != di->device || dq->K != di->K) return KFMI_E_BAD_ARGUMENT;
-  if (!dq->ascii && dq->K == 3) return KFMI_E_BAD_ARGUMENT;
-  const uint64_t ns = strands == KFMI_STRAND_BOTH ? 2 : 1;
-  SearchLaunch a{};
-  a.st = st;
-  a.ix = idx_args(di);
-  int32_t err = use_tables(di, st, a.ix, want, dq->rem);
-  if (err) return err;
-  a.maxw = strand_fused_maxw(di, dq->ascii != nullptr, dq->K, dq->steps, dq->rem);
-  a.words_maxw = a.maxw ? 0 : strand_words_maxw(dq->nwords);
-  if (trace && !a.maxw && !(a.ix.skip && a.words_maxw)) return KFMI_E_NOT_IMPLEMENTED;   /* task_kernel<G, 1, 0, SPLIT> */
-  if (!a.maxw) {
-    err = strand_reserve(dq, dq->num, ctx);
-    if (err) return err;
-  }
-  a.strands = a.maxw ? strands : 0u;
-  a.qp = dq->strand_words;
-  a.ascii = dq->ascii;
-  a.m = dq->size;
-  a.num = a.maxw ? dq->num : ns * dq->num;
-  a.steps = dq->steps;
-  a.nwords = dq->nwords;
-  a.res = d_res;
-  a.trace = trace;
-  HIP_OK(hipEventRecord(ev[0], st));
-  if (!a.maxw) HIP_OK(launch_strand_pack(dq, dq->strand_words, strands, false, st));
-  HIP_OK(hipEventRecord(ev[1], st));
-  if (dq->num) {
-    const Op op = is_coop(di->backend) ? Op::Coop : Op::Task;
-    HIP_OK(trace ? dispatch_strands_trace(di->K, di->nb, di->layout, a) : dispatch(op, di->K, di->nb, di->layout, a));
-  }
-  HIP_OK(hipEventRecord(ev[2], st));
-  return KFMI_SUCCESS;
-}
-
 extern "C" int32_t kfmi_search_strands(void* index, void* queries, void* results, uint32_t strands)
 {
   if (strands < KFMI_STRAND_FWD || strands > KFMI_STRAND_BOTH) return KFMI_E_BAD_ARGUMENT;
@@ -360,21 +290,15 @@ extern "C" int32_t kfmi_search_strands(void* index, void* queries, void* results
   if (r->num != ns * q->num) return KFMI_E_BAD_ARGUMENT;
   DeviceGuard dg;
   std::shared_lock<RwLock> lk(index_lock(f));
-  /* group_transfer cuts the results by r->num, which is not the read slices' */
-  if (f->grp || q->grp || r->grp) return KFMI_E_NOT_IMPLEMENTED;
-  if (!f->dev || !q->dev || !r->d_results) return KFMI_E_NOT_ON_DEVICE;
-  kfmi_dev_index* di = f->dev;
-  if (r->d_device != di->device) return KFMI_E_BAD_ARGUMENT;
-  SearchLane l;
-  int32_t err = search_lane(di->device, &l);
-  const TableWants want = tables_wanted().no_jump();   /* a strand search never takes the text jump */
-  if (!err) err = strands_enqueue(di, q->dev, r->d_results, l.st, l.ev, want, strands, l.ctx);
-  if (!err) err = search_finish(l.st, l.ev, t_ms);
-  return err;
+  const int32_t err = resident_single(f, q, {r});
+  SearchWhat w;
+  w.strands = strands;
+  /* a strand search never takes the text jump */
+  return err ? err : search_run(f, q, r->d_results, tables_wanted().no_jump(), w);
 }
 
 /* kstep_fmi.h: kfmi_search_strands (REV, BOTH) on resident single-device
- * handles with the traced strand kernels -- strands_enqueue itself, so the
+ * handles with the traced strand kernels -- search_enqueue itself, so the
  * tables, the staging, the fetch form and the launch rules are the search's
  * own -- and one record per task copied out.  Everything that has no traced
  * kernel is refused before anything is queued. */
@@ -390,25 +314,12 @@ extern "C" int32_t kfmi_search_strands_trace(void* index, void* queries, void* r
   if (r->num != tasks) return KFMI_E_BAD_ARGUMENT;
   DeviceGuard dg;
   std::shared_lock<RwLock> lk(index_lock(f));
-  if (f->grp || q->grp || r->grp) return KFMI_E_NOT_IMPLEMENTED;
-  if (!f->dev || !q->dev || !r->d_results) return KFMI_E_NOT_ON_DEVICE;
-  kfmi_dev_index* di = f->dev;
-  if (r->d_device != di->device) return KFMI_E_BAD_ARGUMENT;
-  if (is_coop(di->backend) || (di->layout != LAY_INTER && di->layout != LAY_MID) || di->K < 1 || di->K > 2)
-    return KFMI_E_NOT_IMPLEMENTED;
-  SearchLane l;
-  int32_t err = search_lane(di->device, &l);
+  int32_t err = resident_single(f, q, {r});
   if (err) return err;
-  uint4* d_trace = nullptr;
-  if (hipMalloc((void**) &d_trace, 16ull * (tasks ? tasks : 1)) != hipSuccess) {
-    (void) hipGetLastError();
-    return KFMI_E_DEVICE_ALLOC;
-  }
-  err = strands_enqueue(di, q->dev, r->d_results, l.st, l.ev, tables_wanted().no_jump(), strands, l.ctx, d_trace);
-  if (!err) err = search_finish(l.st, l.ev, t_ms);
-  if (!err && tasks && hipMemcpy(trace, d_trace, 16ull * tasks, hipMemcpyDeviceToHost) != hipSuccess) err = KFMI_E_KERNEL;
-  (void) hipFree(d_trace);
-  return err;
+  if (!lane_kernels(f->dev)) return KFMI_E_NOT_IMPLEMENTED;
+  SearchWhat w;
+  w.strands = strands;
+  return search_run(f, q, r->d_results, tables_wanted().no_jump(), w, trace, tasks);
 }
 
 }  // namespace kfmi

@@ -395,11 +395,16 @@ static int32_t stream_on(kfmi_dev_index* di, int member, const char* ascii, uint
   StreamPool& pool = g_pool[di->device][member];
   pool.init = true;
   const int nslot = stream_slots();
+  /* a chunk's geometry, and the plan (kfmi_plan.h) of one sent as ASCII, but for the skip table: whether it packs first */
+  kfmi_dev_queries geo{};
+  geo.size = size;
+  query_geometry(&geo, K);
+  const LaunchPlan ascii_plan = plan_for(di, &geo, true, false, strands, false);
   for (int k = 0; k < nslot; ++k) {
     StreamSlot& s = pool.slot[k];
     err = slot_reserve(s, chunk, size, rows, !pin_in && any_ascii, !pin_out, any_pack, ns);
     /* task columns: for host-packed chunks, and for ASCII ones the task kernel does not pack itself */
-    if (!err && stranded && (any_pack || !strand_fused_maxw(di, true, K, steps, rem))) {
+    if (!err && stranded && (any_pack || ascii_plan.reserve)) {
       s.dq.nwords = nwords;
       err = strand_reserve(&s.dq, chunk, ctx);
     }
@@ -483,31 +488,21 @@ static int32_t stream_on(kfmi_dev_index* di, int member, const char* ascii, uint
     s.dq.nwords = nwords;
     s.dq.rem = rem;
     s.dq.packed_rows = rows;
-    SearchLaunch a;
-    a.st = s.st;
-    a.ix = ix;
-    a.qp = stranded ? s.dq.strand_words : s.dq.packed;
-    a.ascii = s.dq.ascii;
-    a.m = size;
-    /* an ASCII chunk of a strand search packs in the task kernel where that kernel exists
-     * (strand_fused_maxw), like a forward one; else its task columns are written first */
-    a.maxw = host_pack ? 0
-                       : (stranded ? strand_fused_maxw(di, true, K, steps, rem) : fused_maxw(di->backend, K * steps));
-    const bool str_pack = stranded && !a.maxw;
-    a.strands = stranded && a.maxw ? strands : 0u;
-    a.words_maxw = str_pack ? strand_words_maxw(nwords) : 0;
-    a.num = a.strands ? s.n : (uint64_t) ns * s.n;
-    a.steps = steps;
-    a.nwords = nwords;
-    a.res = s.d_res;
+    /* an ASCII chunk packs in the task kernel where that kernel exists, forward or stranded; else its
+     * words or task columns are written first; a host-packed chunk's task columns come from its words */
+    const LaunchPlan p = plan_for(di, &s.dq, !host_pack, false, strands, ix.skip != nullptr);
+    if (p.refusal) {
+      status = p.refusal;
+      break;
+    }
+    const SearchLaunch a = plan_launch(p, s.st, ix, &s.dq, s.d_res);
     void* hdst = pin_out ? (void*) (results + 2 * ns * s.q0) : (void*) s.h_out;
     const bool up_ok = hipEventRecord(s.x0, s.st) == hipSuccess &&
                        (host_pack ? hipMemcpyAsync(s.dq.packed, s.h_pk, 4ull * rows * s.n, hipMemcpyHostToDevice,
                                                    s.st) == hipSuccess
                                   : hipMemcpyAsync(s.dq.ascii, hsrc, bytes, hipMemcpyHostToDevice, s.st) == hipSuccess) &&
                        hipEventRecord(s.x1, s.st) == hipSuccess &&
-                       (str_pack ? launch_strand_pack(&s.dq, s.dq.strand_words, strands, host_pack, s.st) == hipSuccess
-                                 : (host_pack || a.maxw || launch_pack(&s.dq, s.st) == hipSuccess));
+                       plan_pack(p, &s.dq, strands, s.st) == hipSuccess;
     if (!up_ok || dispatch(op, K, di->nb, di->layout, a) != hipSuccess ||
         hipMemcpyAsync(hdst, s.d_res, 8ull * ns * s.n, hipMemcpyDeviceToHost, s.st) != hipSuccess ||
         hipEventRecord(s.done, s.st) != hipSuccess) {

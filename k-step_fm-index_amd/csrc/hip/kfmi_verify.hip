@@ -165,14 +165,6 @@ static hipError_t launch_verify(const VerifyArgs& a, hipStream_t st)
   return hipGetLastError();
 }
 
-/* The device copies the seed search covers: the per-lane kernels on the two
- * plain-counter layouts at K <= 2 ("task", "task-mid") -- the copies the text
- * jump builds its tables for. */
-static bool verify_supported(const kfmi_dev_index* di)
-{
-  return !is_coop(di->backend) && (di->layout == LAY_INTER || di->layout == LAY_MID) && di->K >= 1 && di->K <= 2;
-}
-
 /* The host array of a transferred results handle copied to its device array:
  * caller-filled slots for kfmi_verify_seeds (transferCPUtoGPU zeroes the device
  * array it allocates and copies nothing up). */
@@ -208,17 +200,14 @@ extern "C" int32_t kfmi_verify_seeds(void* index, void* queries, void* intervals
   if (q->size < 1 || q->size > 256) return KFMI_E_BAD_ARGUMENT;
   DeviceGuard dg;
   std::shared_lock<RwLock> lk(index_lock(f));
-  if (f->grp || q->grp || ri->grp || rs->grp || rh->grp) return KFMI_E_NOT_IMPLEMENTED;
-  if (!f->dev || !q->dev || !ri->d_results || !rs->d_results || !rh->d_results) return KFMI_E_NOT_ON_DEVICE;
+  /* the copies the seed search covers, which the text jump builds its tables for, and the ASCII rows */
+  int32_t err = resident_single(f, q, {ri, rs, rh}, NEED_LANE_KERNELS | NEED_ASCII);
+  if (err) return err;
   kfmi_dev_index* di = f->dev;
   kfmi_dev_queries* dq = q->dev;
-  if (!verify_supported(di)) return KFMI_E_NOT_IMPLEMENTED;
-  if (!dq->ascii) return KFMI_E_NOT_IMPLEMENTED;   /* KFMI_UPLOAD=packed: no ASCII rows on the device */
   if (dq->device != di->device || dq->num != q->num || dq->size != q->size) return KFMI_E_BAD_ARGUMENT;
-  if (ri->d_device != di->device || rs->d_device != di->device || rh->d_device != di->device)
-    return KFMI_E_BAD_ARGUMENT;
   SearchLane l;
-  int32_t err = search_lane(di->device, &l);
+  err = search_lane(di->device, &l);
   if (err) return err;
   /* the text jump's tables, built here where the copy has none -- the path
    * kfmi_set_jump(1) takes at a first search, whatever this thread's setting */

@@ -170,6 +170,7 @@ def load() -> ctypes.CDLL:
         "kfmi_search_trace": (i32, [vp, vp, vp, vp]),
         "kfmi_search_strands_trace": (i32, [vp, vp, vp, u32, vp]),
         "kfmi_search_seeds_trace": (i32, [vp, vp, vp, vp, u32, u32, vp]),
+        "kfmi_launch_plan": (i32, [ctypes.c_char_p] + [u32] * 11 + [vp]),
         "kfmi_results_to_device": (i32, [vp]),
         "kfmi_verify_seeds": (i32, [vp, vp, vp, vp, vp, u32, u32, u32, u32]),
         "kfmi_verify_seeds_cpu": (i32, [vp, u64, vp, u64, vp, vp, vp, vp, u32, u32, u32, u32, i32]),
@@ -1031,6 +1032,11 @@ def search_seeds_array(index: Index, reads: np.ndarray, backend: str | None = No
 SEED_TRACE_FIELDS = ("steps", "skip_hits", "skip_misses", "start_hits", "start_empty", "lone_units", "records")
 TRACE_KERNELS = ("seed_kernel", "seed_strands_kernel", "seed_words_kernel", "task_strands_kernel",
                  "task_words_skip_kernel")
+# launch_plan's kernels: those the trace records name, then the forward search's (KFMI_TRACE_KERNEL_TASK_FUSED ..)
+PLAN_KERNELS = TRACE_KERNELS + ("task_kernel fused", "task_kernel tables", "task_kernel jump", "task_kernel words",
+                                "coop_kernel")
+PLAN_FIELDS = ("form", "maxw", "words_maxw", "pack", "kernel")
+PLAN_PACKS = ("none", "forward", "strands from ascii", "strands from words")
 LAUNCH_ID_FIELDS = ("form", "maxw", "kernel", "skip_split", "ftab_folded", "ftab_steps")
 
 
@@ -1065,6 +1071,20 @@ def decode_launch_id(records: np.ndarray) -> dict:
         "ftab_folded": (w >> 16) & 1,
         "ftab_steps": (w >> 24) & 0xFF,
     }
+
+
+def launch_plan(backend: str, k: int, d: int, cls: int, m: int, *, seeds: bool = False, strands: int = 1,
+                ascii: bool = True, fused: bool = True, skip: bool = False, jump: bool = False,
+                traced: bool = False) -> dict:
+    """kfmi_launch_plan: the library's launch plan of one search from values
+    alone (no device, no handle) -- PLAN_FIELDS: the fetch form, maxw,
+    words_maxw, the pack launch (an index into PLAN_PACKS) and the kernel (an
+    index into PLAN_KERNELS).  A refused call raises KfmiError with its code."""
+    out = (ctypes.c_int32 * 5)()
+    _check(load().kfmi_launch_plan(backend.encode(), int(k), int(d), int(cls), int(m), int(bool(seeds)), int(strands),
+                                   int(bool(ascii)), int(bool(fused)), int(bool(skip)), int(bool(jump)), int(bool(traced)),
+                                   out), "kfmi_launch_plan")
+    return dict(zip(PLAN_FIELDS, (int(v) for v in out)))
 
 
 def search_strands_trace(index: Index, reads: np.ndarray, backend: str | None = None, strands: int = STRAND_BOTH):

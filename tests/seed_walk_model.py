@@ -14,7 +14,10 @@ intervals and spans of the records ([T, S, 2], unused slots zero).
 expected_form() is the fetch form launch_seeds and launch_task pick per
 geometry, table-size class and code registers: the table of
 test_fetch_forms.py's docstring as a function, and expected_launch() the rest of
-a record's word 3.
+a record's word 3.  expected_forward_launch() is the same for the forward search,
+whose records carry no launch identity: the launch plan's rules (DESIGN.md
+"launch plan") written out again, for tests/test_launch_plan.py to hold the
+library's own plan to.
 """
 import numpy as np
 
@@ -22,6 +25,8 @@ FIELDS = ("steps", "skip_hits", "skip_misses", "start_hits", "start_empty", "lon
 ACGT = np.frombuffer(b"ACGT", np.uint8)
 FWD, REV, BOTH = 1, 2, 3
 SEED_KERNEL, SEED_STRANDS_KERNEL, SEED_WORDS_KERNEL, TASK_STRANDS_KERNEL, TASK_WORDS_SKIP_KERNEL = range(5)
+TASK_FUSED_KERNEL, TASK_TABLES_KERNEL, TASK_JUMP_KERNEL, TASK_WORDS_KERNEL, COOP_KERNEL = range(5, 10)
+PACK_NONE, PACK_FORWARD, PACK_STRANDS_ASCII, PACK_STRANDS_WORDS = range(4)
 
 
 def play(world, k, tasks, ftab_steps=0, skip=False, s=8):
@@ -117,18 +122,25 @@ def classes(mod, m):
 
 
 LOOKUPS = ("start_hit", "start_empty", "skip_hit", "skip_miss")
-ASM = {(2, 64), (1, 128)}                                       # the asm fetch: forms 8 / 7
-SMALL = {(1, 64), (1, 32), (2, 128)}                            # one line per block, the C++ fetch: forms 1 / 4
-STREAM = {(2, 192)}                                             # lf_stream whatever the form: 1
-TASK_ONLY_MID = {(1, 32), (2, 128), (2, 192)}
+D_ALL = (32, 64, 128, 192, 256, 448, 960)                       # every d the kernels are built for, K = 1 and 2
+GEOMETRIES = [(k, d) for k in (1, 2) for d in D_ALL]
+
+
+def bitmap_words(k, d):
+    return 2 * k * d // 32
+
+
+ASM = {g for g in GEOMETRIES if bitmap_words(*g) == 8}                        # the asm fetch: forms 8 / 7
+SMALL = {g for g in GEOMETRIES if bitmap_words(*g) <= 16} - ASM               # one line per block, the C++ fetch: 1 / 4
+STREAM = set(GEOMETRIES) - ASM - SMALL                                        # lf_stream whatever the form: 1
+assert ASM == {(2, 64), (1, 128)} and {(1, 64), (1, 32), (2, 128)} <= SMALL and (2, 192) in STREAM
 
 
 def expected_form(layout, k, d, cls, maxw):
     """The SPLIT template value of the seed or strand kernel launched for this
     geometry at table-size class cls (0 = by size: 1 on a small index) with
-    maxw code registers."""
-    assert layout in ("task-mid", "task") and cls in (0, 1, 2, 4) and maxw in (8, 16), (layout, cls, maxw)
-    assert layout == "task-mid" or (k, d) not in TASK_ONLY_MID, (layout, k, d)
+    maxw code registers (0: the plain walk of packed words)."""
+    assert layout in ("task-mid", "task") and cls in (0, 1, 2, 4) and maxw in (0, 8, 16), (layout, cls, maxw)
     cls = cls or 1
     if (k, d) in ASM:
         return 8 if cls == 1 else 7
@@ -159,3 +171,23 @@ def expected_launch(layout, k, d, cls, m, strands, fused, ftab_steps, skip, seed
     steps = 0 if m % k else ftab_steps
     return {"form": expected_form(layout, k, d, cls, maxw), "maxw": maxw, "kernel": kernel,
             "skip_split": (cls or 1) if skip else 1, "ftab_folded": int(bool(folded and steps)), "ftab_steps": steps}
+
+
+def expected_forward_launch(layout, k, d, cls, m, fused, ascii, skip, jump, traced=False):
+    """The launch plan of kfmi_search (kstep_fmi.launch_plan's fields), or the
+    code the traced call is refused with.  The kernel packs the ASCII rows
+    itself up to 256 bases in K-steps under the fused knob; everything else
+    walks packed words plainly -- the pack launch's, or the host's -- whatever
+    the tables in effect, and has no traced form."""
+    bases = m - m % k
+    maxw = (8 if bases <= 128 else 16 if bases <= 256 else 0) if fused and ascii else 0
+    if traced and not maxw:
+        return 19                                                # KFMI_E_NOT_IMPLEMENTED
+    if not maxw:
+        kernel = TASK_WORDS_KERNEL
+    elif jump:
+        kernel = TASK_JUMP_KERNEL
+    else:
+        kernel = TASK_TABLES_KERNEL if skip or traced else TASK_FUSED_KERNEL
+    return {"form": expected_form(layout, k, d, cls, maxw), "maxw": maxw, "words_maxw": 0,
+            "pack": PACK_FORWARD if ascii and not maxw else PACK_NONE, "kernel": kernel}

@@ -190,6 +190,22 @@ def same_launch(K, rec, want, what):
                                      None if f != "kernel" else K.TRACE_KERNELS[v])
 
 
+def plan_of(K, geo, cls, m, strands, fused, skip, seeds):
+    """The library's own launch plan of the traced call (kfmi_launch_plan, no
+    device): class 0 is class 1 on these texts, and the one-shot calls upload
+    ASCII rows."""
+    backend, k, d = geo
+    return K.launch_plan(backend, k, d, cls or 1, m, seeds=seeds, strands=strands, ascii=True, fused=fused, skip=skip,
+                         traced=True)
+
+
+def same_plan(K, rec, plan, what):
+    """Word 3 as the device reports it is what the host plan says it launches."""
+    got = K.decode_launch_id(rec)
+    for f, v in (("form", plan["form"]), ("maxw", plan["maxw"] or plan["words_maxw"]), ("kernel", plan["kernel"])):
+        assert (got[f] == v).all(), (what, "word 3 against kfmi_launch_plan", f, sorted(set(got[f].tolist())), "plan", plan)
+
+
 def check_seeds(K, oracle_mod, idx, name, geo, cls, m, s, strands, fused, ftab, skip, folded, num=None, n_reads=192):
     """One seed search: records three ways, every field of every trace record, word 3."""
     backend, k, d = geo
@@ -209,6 +225,7 @@ def check_seeds(K, oracle_mod, idx, name, geo, cls, m, s, strands, fused, ftab, 
     assert tuple(dec) == swm.FIELDS == K.SEED_TRACE_FIELDS
     same_fields(dec, {f: mod[f][rows] for f in swm.FIELDS}, swm.FIELDS, what)
     same_launch(K, rec, swm.expected_launch(backend, k, d, cls, m, strands, fused, f_steps, skip, True, folded), what)
+    same_plan(K, rec, plan_of(K, geo, cls, m, strands, fused, skip, True), what)
 
 
 STRAND_FIELDS = ("steps", "skip_hits", "skip_misses", "start_steps")
@@ -226,6 +243,9 @@ def check_strands(K, oracle_mod, idx, name, geo, cls, m, strands, fused, ftab, s
         with pytest.raises(K.KfmiError) as e:
             K.search_strands_trace(idx, q, backend, strands)
         assert e.value.code == NOT_IMPLEMENTED, what
+        with pytest.raises(K.KfmiError) as e:                    # and the host plan refuses what the call refused
+            plan_of(K, geo, cls, m, strands, fused, skip, False)
+        assert e.value.code == NOT_IMPLEMENTED, what
         return
     mod = strand_model(name, k, m, f_steps, skip, n_reads)
     got, rec = K.search_strands_trace(idx, q, backend, strands)
@@ -239,6 +259,7 @@ def check_strands(K, oracle_mod, idx, name, geo, cls, m, strands, fused, ftab, s
     same_fields(dec, {f: mod[f][rows] for f in STRAND_FIELDS}, STRAND_FIELDS, what)
     assert (rec[:, 1] == 0).all() and (rec[:, 2] >> 31 == 0).all(), (what, "a strand search never takes the text jump")
     same_launch(K, rec, want, what)
+    same_plan(K, rec, plan_of(K, geo, cls, m, strands, fused, skip, False), what)
 
 
 def check_all(K, oracle_mod, idx, name, geo, cls, lengths, fused, ftab, skip, folded):
