@@ -771,6 +771,58 @@ int32_t kfmi_verify_seeds_cpu(const char *text, uint64_t n, const uint32_t *sa, 
                               int32_t nthreads);
 int32_t kfmi_results_to_device(void *results);
 
+/* ---- align seeds (not in the reference, which stops at intervals) ------------
+ * "verify seeds" with a banded edit distance in place of the Hamming count, so
+ * that a read with an inserted or deleted base is placed too.  Tasks, their
+ * order, the S = max_seeds slots per task, the strand modes, the three handles
+ * and their sizes, the candidates of a slot (rows L, L + 1, .. below min(R,
+ * rows, L + max_occ)), the ignored-slot forms, which candidates are scored
+ * (sa[r] < rows, p >= start, o + m <= n with o = p - start) and the `scored`
+ * count are those of "verify seeds".  What changes is a candidate's score and
+ * what x and KFMI_HIT_MULTI mean.
+ *   Score of a scored candidate with origin o under band w, 0 <= w <=
+ * KFMI_ALIGN_MAX_BAND.  Cells are (i, d) with 0 <= i <= m and -w <= d <= w;
+ * cell (i, d) stands at text position j = o + i + d and is valid iff 0 <= j <=
+ * n.  A(i, d) is the least number of edits that align P[i .. m) to text
+ * beginning at j and ending anywhere inside the band: A(m, d) = 0 for valid d,
+ * and for i < m and a valid cell the minimum, over the transitions that exist,
+ * of
+ *     A(i+1, d)   + [base2index(P[i]) != code(T[j])]   when j < n,
+ *     A(i+1, d-1) + 1   when d - 1 >= -w      (a read base with no text base),
+ *     A(i, d+1)   + 1   when d + 1 <= w and j < n      (a text base skipped);
+ * invalid cells are +infinity.  The candidate's edits are e = min over d of
+ * A(0, d), its begin positions every o + d with A(0, d) = e.  d = 0 is valid in
+ * every row of a scored candidate, so e never exceeds the Hamming count, and
+ * with w = 0 it is the Hamming count.  (The prefix form -- a free start in the
+ * band, rows 0 -> m, the minimum at row m -- gives the same e; the suffix form
+ * is the definition because its last row carries the begin positions.)
+ *   Record.  E is the least e over the task's scored candidates, B_min and
+ * B_max the smallest and the largest begin position over all (candidate, d)
+ * pairs that attain E.  If E <= max_edits: x = B_min, y = E | KFMI_HIT_MULTI
+ * iff B_max - B_min > 2w | scored << 20.  Otherwise, and with no scored
+ * candidate: x = KFMI_HIT_NONE, y = scored << 20.  Nothing depends on the
+ * evaluation order.  Two seeds on either side of one indel imply origins that
+ * differ by the indel's length and lead to one begin position, which is why
+ * MULTI looks at the spread of begin positions and not at distinct origins.
+ * With band = 0 every record equals kfmi_verify_seeds' bit for bit.
+ *   What a record does not hold: the alignment itself (no traceback, no CIGAR)
+ * and its end position; costs are 1 per substitution, inserted or deleted
+ * base; an indel longer than the band is not found.
+ *   Arguments, coverage, refusals, the tables built on demand and
+ * kfmi_last_timing (total, 0, the align kernel) are exactly those of
+ * kfmi_verify_seeds; band > KFMI_ALIGN_MAX_BAND is KFMI_E_BAD_ARGUMENT;
+ * max_edits may be any value.  A refused call writes nothing.
+ *   kfmi_align_seeds_cpu: the same definition on the host, with the arguments
+ * of kfmi_verify_seeds_cpu. */
+#define KFMI_ALIGN_MAX_BAND 15u
+int32_t kfmi_align_seeds(void *index, void *queries, void *intervals, void *spans, void *hits,
+                         uint32_t max_seeds, uint32_t strands, uint32_t max_occ,
+                         uint32_t band, uint32_t max_edits);
+int32_t kfmi_align_seeds_cpu(const char *text, uint64_t n, const uint32_t *sa, uint64_t rows,
+                             void *queries, void *intervals, void *spans, void *hits,
+                             uint32_t max_seeds, uint32_t strands, uint32_t max_occ,
+                             uint32_t band, uint32_t max_edits, int32_t nthreads);
+
 /* ---- walk trace (tests and diagnosis; not in the reference, not timed) -------
  * The fused forward task kernel ends a walk early through three shortcuts --
  * the jump start, the skip table and the text jump (DESIGN.md 5a .. 5a''') --

@@ -36,18 +36,9 @@
 #include "../kfmi_internal.h"
 #include "kfmi_device.h"
 #include "kfmi_runtime.h"
+#include "kfmi_verify.h"
 
 namespace kfmi {
-
-struct VerifyArgs {
-  const uint8_t* __restrict__ ascii;   /* num reads of m bases */
-  const uint2* __restrict__ iv;        /* S slots per task: {L, R} */
-  const uint2* __restrict__ sp;        /* S slots per task: {start, len} */
-  uint2* __restrict__ hits;            /* one record per task */
-  const uint32_t* __restrict__ jsa;    /* [sa | isa | text] */
-  uint64_t num;
-  uint32_t m, strands, S, rows, max_occ, max_mism, split4;
-};
 
 /* STR: the strand staging (a.strands 2 = REV, 3 = BOTH: task 2q + strand), else forward reads. */
 template <int MAXW, bool STR>
@@ -149,7 +140,7 @@ __global__ __launch_bounds__(256) void verify_kernel(VerifyArgs a)
                   : make_uint2(KFMI_HIT_NONE, scored << KFMI_HIT_SCORED_SHIFT);
 }
 
-static hipError_t launch_verify(const VerifyArgs& a, hipStream_t st)
+static hipError_t launch_verify(const VerifyArgs& a, uint32_t band, hipStream_t st)
 {
   const bool str = a.strands != KFMI_STRAND_FWD;
   const uint64_t tasks = (a.strands == KFMI_STRAND_BOTH ? 2u : 1u) * a.num;
@@ -183,8 +174,8 @@ extern "C" int32_t kfmi_results_to_device(void* results)
   return KFMI_SUCCESS;
 }
 
-extern "C" int32_t kfmi_verify_seeds(void* index, void* queries, void* intervals, void* spans, void* hits,
-                                     uint32_t max_seeds, uint32_t strands, uint32_t max_occ, uint32_t max_mism)
+int32_t seed_score_call(void* index, void* queries, void* intervals, void* spans, void* hits, uint32_t max_seeds,
+                        uint32_t strands, uint32_t max_occ, uint32_t band, uint32_t bound, SeedScoreLaunch launch)
 {
   if (max_seeds < 1 || max_seeds > 8) return KFMI_E_BAD_ARGUMENT;
   if (strands < KFMI_STRAND_FWD || strands > KFMI_STRAND_BOTH) return KFMI_E_BAD_ARGUMENT;
@@ -227,16 +218,23 @@ extern "C" int32_t kfmi_verify_seeds(void* index, void* queries, void* intervals
   a.S = max_seeds;
   a.rows = di->bwtsize;
   a.max_occ = max_occ;
-  a.max_mism = max_mism;
+  a.max_mism = bound;
   a.split4 = split_for(8ull * di->bwtsize, LAY_INTER) == 4u ? 1u : 0u;
   HIP_OK(hipEventRecord(l.ev[0], l.st));
   HIP_OK(hipEventRecord(l.ev[1], l.st));
-  if (dq->num) HIP_OK(launch_verify(a, l.st));
+  if (dq->num) HIP_OK(launch(a, band, l.st));
   HIP_OK(hipEventRecord(l.ev[2], l.st));
   err = search_finish(l.st, l.ev, t_ms);
-  t_ms[0] = t_ms[2];   /* total, 0, the verify kernel: nothing is packed beforehand */
+  t_ms[0] = t_ms[2];   /* total, 0, the kernel: nothing is packed beforehand */
   t_ms[1] = 0.0;
   return err;
+}
+
+extern "C" int32_t kfmi_verify_seeds(void* index, void* queries, void* intervals, void* spans, void* hits,
+                                     uint32_t max_seeds, uint32_t strands, uint32_t max_occ, uint32_t max_mism)
+{
+  return seed_score_call(index, queries, intervals, spans, hits, max_seeds, strands, max_occ, 0u, max_mism,
+                         launch_verify);
 }
 
 }  // namespace kfmi

@@ -19,8 +19,8 @@
 
 /* One task: p its m bases, iv / sp its S slots; returns the record's two words. */
 static void vs_task(const uint8_t *text, uint64_t n, const uint32_t *sa, uint64_t rows, const uint8_t *p, uint32_t m,
-                    const uint32_t *iv, const uint32_t *sp, uint32_t S, uint32_t max_occ, uint32_t max_mism,
-                    uint32_t *hit)
+                    const uint32_t *iv, const uint32_t *sp, uint32_t S, uint32_t max_occ, uint32_t band,
+                    uint32_t max_mism, uint32_t *hit)
 {
   uint32_t best_m = 0xFFFFFFFFu, best_o = 0xFFFFFFFFu, multi = 0, scored = 0, s, j;
   uint8_t pc[256];
@@ -58,9 +58,11 @@ static void vs_task(const uint8_t *text, uint64_t n, const uint32_t *sa, uint64_
   }
 }
 
-int32_t kfmi_verify_seeds_cpu(const char *text, uint64_t n, const uint32_t *sa, uint64_t rows, void *queries,
-                              void *intervals, void *spans, void *hits, uint32_t max_seeds, uint32_t strands,
-                              uint32_t max_occ, uint32_t max_mism, int32_t nthreads)
+/* The argument checks, the reverse complements and the loop over the tasks,
+ * shared with kfmi_align_seeds_cpu (align.c): `task` scores one task. */
+int32_t kfmi_seed_tasks_cpu(const char *text, uint64_t n, const uint32_t *sa, uint64_t rows, void *queries,
+                            void *intervals, void *spans, void *hits, uint32_t max_seeds, uint32_t strands,
+                            uint32_t max_occ, uint32_t band, uint32_t bound, int32_t nthreads, kfmi_seed_task_fn task)
 {
   const kfmi_qrys_t *q = (const kfmi_qrys_t *) queries;
   const kfmi_res_t *ri = (const kfmi_res_t *) intervals, *rs = (const kfmi_res_t *) spans;
@@ -96,10 +98,18 @@ int32_t kfmi_verify_seeds_cpu(const char *text, uint64_t n, const uint32_t *sa, 
     const uint64_t r = ns == 2u ? (uint64_t) t >> 1 : (uint64_t) t;
     const int back = strands == KFMI_STRAND_REV || (ns == 2u && (t & 1));
     const uint8_t *p = (const uint8_t *) (back ? rev : q->h_queries) + r * q->size;
-    vs_task((const uint8_t *) text, n, sa, rows, p, q->size, ri->h_results + 2 * (uint64_t) t * S,
-            rs->h_results + 2 * (uint64_t) t * S, S, max_occ, max_mism, rh->h_results + 2 * (uint64_t) t);
+    task((const uint8_t *) text, n, sa, rows, p, q->size, ri->h_results + 2 * (uint64_t) t * S,
+         rs->h_results + 2 * (uint64_t) t * S, S, max_occ, band, bound, rh->h_results + 2 * (uint64_t) t);
   }
   kfmi_big_free(rev);
   rh->origin = KFMI_RES_FROM_CPU;
   return KFMI_SUCCESS;
+}
+
+int32_t kfmi_verify_seeds_cpu(const char *text, uint64_t n, const uint32_t *sa, uint64_t rows, void *queries,
+                              void *intervals, void *spans, void *hits, uint32_t max_seeds, uint32_t strands,
+                              uint32_t max_occ, uint32_t max_mism, int32_t nthreads)
+{
+  return kfmi_seed_tasks_cpu(text, n, sa, rows, queries, intervals, spans, hits, max_seeds, strands, max_occ, 0u,
+                             max_mism, nthreads, vs_task);
 }

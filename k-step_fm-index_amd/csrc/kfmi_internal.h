@@ -96,6 +96,17 @@ typedef struct {
   char    *h_reference;
 } kfmi_ref_t;
 
+/* verify.c: what kfmi_verify_seeds_cpu and kfmi_align_seeds_cpu share -- the
+ * argument checks, the reverse complements of REV / BOTH and the OpenMP loop
+ * over the tasks; `task` forms one task's record from its m bases and S slots */
+typedef void (*kfmi_seed_task_fn)(const uint8_t *text, uint64_t n, const uint32_t *sa, uint64_t rows,
+                                  const uint8_t *p, uint32_t m, const uint32_t *iv, const uint32_t *sp, uint32_t S,
+                                  uint32_t max_occ, uint32_t band, uint32_t bound, uint32_t *hit);
+int32_t kfmi_seed_tasks_cpu(const char *text, uint64_t n, const uint32_t *sa, uint64_t rows, void *queries,
+                            void *intervals, void *spans, void *hits, uint32_t max_seeds, uint32_t strands,
+                            uint32_t max_occ, uint32_t band, uint32_t bound, int32_t nthreads,
+                            kfmi_seed_task_fn task);
+
 /* fmi_index.c */
 /* Host entries of an index whose entries are only on the device (fetched once,
  * then kept); KFMI_SUCCESS at once when the host image exists (kfmi_build.hip). */

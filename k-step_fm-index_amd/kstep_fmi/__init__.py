@@ -174,6 +174,8 @@ def load() -> ctypes.CDLL:
         "kfmi_results_to_device": (i32, [vp]),
         "kfmi_verify_seeds": (i32, [vp, vp, vp, vp, vp, u32, u32, u32, u32]),
         "kfmi_verify_seeds_cpu": (i32, [vp, u64, vp, u64, vp, vp, vp, vp, u32, u32, u32, u32, i32]),
+        "kfmi_align_seeds": (i32, [vp, vp, vp, vp, vp, u32, u32, u32, u32, u32]),
+        "kfmi_align_seeds_cpu": (i32, [vp, u64, vp, u64, vp, vp, vp, vp, u32, u32, u32, u32, u32, i32]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -1141,6 +1143,7 @@ HIT_MISM_MASK = 0x0000FFFF
 HIT_MULTI = 0x00010000
 HIT_SCORED_SHIFT = 20
 VERIFY_MAX_OCC = 256
+ALIGN_MAX_BAND = 15
 
 
 def results_to_gpu(results: Results) -> None:
@@ -1174,6 +1177,29 @@ def verify_seeds_cpu(text, sa: np.ndarray, queries: Queries, intervals: Results,
            "kfmi_verify_seeds_cpu")
 
 
+def align_seeds(index: Index, queries: Queries, intervals: Results, spans: Results, hits: Results, max_seeds: int,
+                strands: int, max_occ: int, band: int, max_edits: int) -> None:
+    """kfmi_align_seeds: verify_seeds with a banded edit distance (band 0 ..
+    ALIGN_MAX_BAND cells either side of each seed's origin) in place of the
+    Hamming count.  Entry t of `hits`: x = the smallest begin position of a
+    best placement or HIT_NONE, y = edits | HIT_MULTI (best placements begin
+    more than 2 * band apart) | scored << HIT_SCORED_SHIFT."""
+    _check(load().kfmi_align_seeds(index.ptr, queries.ptr, intervals.ptr, spans.ptr, hits.ptr, int(max_seeds),
+                                   int(strands), int(max_occ), int(band), int(max_edits)), "kfmi_align_seeds")
+
+
+def align_seeds_cpu(text, sa: np.ndarray, queries: Queries, intervals: Results, spans: Results, hits: Results,
+                    max_seeds: int, strands: int, max_occ: int, band: int, max_edits: int, nthreads: int = 0) -> None:
+    """kfmi_align_seeds_cpu: the same records on the host, with the arguments of verify_seeds_cpu."""
+    t = np.ascontiguousarray(np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text,
+                             dtype=np.uint8)
+    sa = np.ascontiguousarray(sa, dtype=np.uint32)
+    _check(load().kfmi_align_seeds_cpu(t.ctypes.data_as(ctypes.c_void_p), t.size, sa.ctypes.data_as(ctypes.c_void_p),
+                                       sa.size, queries.ptr, intervals.ptr, spans.ptr, hits.ptr, int(max_seeds),
+                                       int(strands), int(max_occ), int(band), int(max_edits), int(nthreads)),
+           "kfmi_align_seeds_cpu")
+
+
 def decode_hits(hits: np.ndarray):
     """(origin int64 with -1 for none, mism, multi, scored) of uint32 [T, 2] hit records."""
     h = np.asarray(hits, dtype=np.uint32).reshape(-1, 2)
@@ -1185,17 +1211,23 @@ def decode_hits(hits: np.ndarray):
 
 def map_reads_array(index: Index, reads: np.ndarray, backend: str | None = None, max_seeds: int = 4,
                     strands: int = STRAND_BOTH, max_occ: int = 8, max_mism: int | None = None, cpu: bool = False,
-                    text=None):
+                    text=None, band: int | None = None, max_edits: int | None = None):
     """Upload, seed search and verify of uint8 [N, m] reads in one call: where
     each task maps and with how many differences.  Returns (origin, mism, multi,
     scored), arrays of ns * N tasks (BOTH: task 2q + strand): origin -1 and
     mism 0 where no scored candidate has at most max_mism mismatches (None:
     no bound).  cpu=True runs both steps on the host and needs `text`, the
     indexed text; the suffix array is the index's own at sampling rate 1, else
-    that of a temporary index of `text`."""
+    that of a temporary index of `text`.
+    band=None scores candidates by their Hamming count (verify_seeds).  An
+    integer band takes align_seeds instead: origin is then the begin position
+    of the best banded placement, mism its edits, bounded by max_edits (None:
+    max_mism's value) -- reads with an indel of up to `band` bases map too."""
     n, s = reads.shape[0], int(max_seeds)
     ns = _strand_count(strands)
     mm = 0xFFFFFFFF if max_mism is None else int(max_mism)
+    if band is not None and max_edits is not None:
+        mm = int(max_edits)
     if backend and not cpu:
         set_backend(backend)
     q = Queries.from_array(reads)
@@ -1210,13 +1242,19 @@ def map_reads_array(index: Index, reads: np.ndarray, backend: str | None = None,
                 tmp = Index.build(bytes(text), k=1, d=64, sa_rate=1)
                 rate, sa = tmp.sa()
             search_seeds_cpu(index, q, iv, sp, s, strands)
-            verify_seeds_cpu(text, sa, q, iv, sp, hits, s, strands, max_occ, mm)
+            if band is None:
+                verify_seeds_cpu(text, sa, q, iv, sp, hits, s, strands, max_occ, mm)
+            else:
+                align_seeds_cpu(text, sa, q, iv, sp, hits, s, strands, max_occ, band, mm)
         else:
             transfer_to_gpu(index, q, iv)
             transfer_to_gpu(index, None, sp)
             transfer_to_gpu(index, None, hits)
             search_seeds(index, q, iv, sp, s, strands)
-            verify_seeds(index, q, iv, sp, hits, s, strands, max_occ, mm)
+            if band is None:
+                verify_seeds(index, q, iv, sp, hits, s, strands, max_occ, mm)
+            else:
+                align_seeds(index, q, iv, sp, hits, s, strands, max_occ, band, mm)
             transfer_to_cpu(hits)
         return decode_hits(hits.array().copy())
     finally:
