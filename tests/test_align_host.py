@@ -12,7 +12,10 @@
   without a suffix) at max_occ 1, 7, 256;
 * the refusals return 33 and write nothing;
 * the header's and the binding's symbols are there;
-* tests/asan/align_asan.c runs clean under AddressSanitizer + UBSan."""
+* tests/asan/align_asan.c runs clean under AddressSanitizer + UBSan;
+* tests/asan/align_dp_host.cpp: the kernel's own arithmetic (csrc/hip/
+  kfmi_align_dp.h, compiled for the host) equals a plain full-table DP, under
+  the same sanitizers, on low-complexity texts at every band."""
 import os
 import re
 import shutil
@@ -230,3 +233,44 @@ def test_align_clean_under_asan(tmp_path):
                UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1", OMP_NUM_THREADS="4")
     p = subprocess.run([str(out)], capture_output=True, text=True, env=env, timeout=300)
     assert p.returncode == 0 and p.stdout.startswith("OK"), p.stdout[-2000:] + p.stderr[-4000:]
+
+
+def planned_dp_cases() -> dict:
+    """The cases tests/asan/align_dp_host.cpp says it runs, counted here from its
+    header's description and not from its loops."""
+    kinds, bands = 6, 16
+    sweep_n, sweep_m, pin_m = (40, 257, 300, 303, 320), (1, 2, 15, 16, 17, 33, 100, 128, 129, 255, 256), (17, 100, 129, 256)
+    fits = lambda m, k: 3 * k <= m                                       # noqa: E731
+    beside = lambda w: 1 + (w > 1) + (w < 15)                            # noqa: E731  the band and the bands beside it
+    return {
+        "sweep": kinds * sum(sum(m <= n for m in sweep_m) for n in sweep_n) * bands * (16 + 16 + 8),
+        "ends": kinds * 2 * bands * sum(32 * len(ar.pinned(m)) * 2 for m in pin_m),
+        "edge": kinds * 3 * len(pin_m) * 15 * 3 * 2,
+        "indel": kinds * 3 * sum(3 * beside(w) * 2 for m in pin_m for w in range(1, 16) for k in (w, w + 1) if fits(m, k)),
+        "leave": kinds * 3 * sum(3 * beside(w) for m in pin_m for w in range(1, 16) if fits(m, w + 1)),
+        "comeback": kinds * 3 * sum(3 * beside(w) for m in pin_m for w in range(1, 16) if fits(m, w + 1)),
+    }
+
+
+def test_dp_header_equals_the_definition_under_asan(tmp_path):
+    """tests/asan/align_dp_host.cpp: csrc/hip/kfmi_align_dp.h compiled for the
+    host under -fsanitize=address,undefined, band_rows<8>, band_rows<16> and
+    band_fold against a plain full-table DP on low-complexity texts, every
+    band, both text ends, band-edge placements and indels of w and w + 1 bases.
+    A stand-alone program; every family must have run its planned cases."""
+    if not shutil.which("g++"):
+        pytest.skip("g++ not available")
+    out = tmp_path / "align_dp_host"
+    cmd = ["g++", "-g", "-O1", "-std=c++17", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
+           "-fno-sanitize-recover=undefined", "-o", str(out), str(util.REPO / "tests" / "asan" / "align_dp_host.cpp")]
+    subprocess.run(cmd, check=True, capture_output=True, text=True)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:exitcode=23",
+               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    p = subprocess.run([str(out)], capture_output=True, text=True, env=env, timeout=300)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+    lines = dict(ln.split() for ln in p.stdout.strip().splitlines())
+    plan = planned_dp_cases()
+    assert plan["sweep"] >= 185_280
+    for family, want in plan.items():
+        assert int(lines[family]) >= want, (family, lines[family], want)
+    assert int(lines["OK"]) >= sum(plan.values()), (lines["OK"], plan)
