@@ -806,7 +806,7 @@ int32_t kfmi_results_to_device(void *results);
  * MULTI looks at the spread of begin positions and not at distinct origins.
  * With band = 0 every record equals kfmi_verify_seeds' bit for bit.
  *   What a record does not hold: the alignment itself (no traceback, no CIGAR)
- * and its end position; costs are 1 per substitution, inserted or deleted
+ * and its end position, which kfmi_align_paths forms from x; costs are 1 per substitution, inserted or deleted
  * base; an indel longer than the band is not found.
  *   Arguments, coverage, refusals, the tables built on demand and
  * kfmi_last_timing (total, 0, the align kernel) are exactly those of
@@ -822,6 +822,99 @@ int32_t kfmi_align_seeds_cpu(const char *text, uint64_t n, const uint32_t *sa, u
                              void *queries, void *intervals, void *spans, void *hits,
                              uint32_t max_seeds, uint32_t strands, uint32_t max_occ,
                              uint32_t band, uint32_t max_edits, int32_t nthreads);
+
+/* ---- align paths (not in the reference, which stops at intervals) ------------
+ * The alignment itself: for every task the CIGAR and the end position of its
+ * placement at a given begin position, under the costs and the band of "align
+ * seeds".  Tasks, their order and the strand modes are those of
+ * kfmi_align_seeds (ns = 2 for BOTH, task t = 2q + strand; a REV task is the
+ * read P', and its CIGAR is in P' order against the forward text).
+ *   Handles.  `hits`: a results handle of ns * num entries as kfmi_align_seeds
+ * or kfmi_verify_seeds leaves it on the device -- caller-filled handles sent up
+ * with kfmi_results_to_device are accepted too; only word x of an entry is
+ * read, the begin position B or KFMI_HIT_NONE.  `paths`: a handle of exactly
+ * ns * num entries.  `cigars`: a handle of exactly ns * num * C entries, C =
+ * cigar_entries in 1 .. KFMI_PATH_MAX_ENTRIES; task t owns the entries t * C ..
+ * t * C + C - 1, which are 2C u32 words, one per run.  Every entry of `paths`
+ * and `cigars` is written, whatever it held before.
+ *   Definition.  n is the text's length, m the read length, w = band with 0 <=
+ * w <= KFMI_ALIGN_MAX_BAND.  A task has no path when x = KFMI_HIT_NONE, n < m,
+ * B > n, or B - c > w, where c = min(B, n - m) is the band's centre.  Otherwise
+ * cells are (i, d) with 0 <= i <= m and -w <= d <= w; cell (i, d) stands at
+ * text position j = c + i + d and is valid iff 0 <= j <= n.  A(i, d) is the
+ * least number of edits that align P[i .. m) to text beginning at j and ending
+ * anywhere inside the band: A(m, d) = 0 for valid d, and for i < m and a valid
+ * cell the minimum, over the transitions that exist, of
+ *     A(i+1, d)   + [base2index(P[i]) != code(T[j])]   when j < n,
+ *     A(i+1, d-1) + 1   when d - 1 >= -w      (a read base with no text base),
+ *     A(i, d+1)   + 1   when d + 1 <= w and j < n      (a text base skipped);
+ * invalid cells are +infinity.  That is the table of "align seeds" with o := c.
+ * With d0 = B - c the task's edits are D = A(0, d0), which is finite; if D >
+ * max_edits the task has no path.
+ *   The path is one walk from (0, d0) with v = D.  While i < m, take the first
+ * of these that exists and attains v (invalid cells attain nothing):
+ *     1. text base skipped: d + 1 <= w, j < n and A(i, d+1) + 1 = v.
+ *        Op D, d += 1, v -= 1.
+ *     2. read base with no text base: d - 1 >= -w and A(i+1, d-1) + 1 = v.
+ *        Op I, i += 1, d -= 1, v -= 1.
+ *     3. diagonal: j < n and A(i+1, d) + [base2index(P[i]) != code(T[j])] = v.
+ *        Op = or X, i += 1, v -= that bracket.
+ * The walk stops when i = m: the end is free inside the band, so no D follows
+ * the last read base.  Gaps come first, so a gap in a repeat sits at its
+ * leftmost place in read order, the usual normal form.  The result depends on
+ * no evaluation order.
+ *   Record.  paths[t]: x = the end position c + m + d, one past the last text
+ * base used; y = D | runs << KFMI_PATH_RUNS_SHIFT | KFMI_PATH_OVERFLOW, runs
+ * the number of runs of the path (12 bits).  cigars: run r of the task is the
+ * u32 word len << 4 | op with BAM's codes I = 1, D = 2, '=' = 7, X = 8, runs
+ * in read order; unused words are 0 and no run has length 0.  A path of more
+ * than 2C runs leaves every word of the task 0 and sets KFMI_PATH_OVERFLOW,
+ * with `runs` the number needed and x and D as usual; a path has at most 2D +
+ * 1 runs, so C >= max_edits + 1 never overflows.  No path: x = KFMI_HIT_NONE,
+ * y = 0, every word 0.
+ *   What holds of every record with a path that fits:
+ *     the lengths of its =, X and I runs sum to m;
+ *     B plus the lengths of its =, X and D runs is x;
+ *     the lengths of its X, I and D runs sum to D;
+ *     replaying the runs over P and T finds equal bases under = and different
+ *     ones under X;
+ *     with w = 0 the path is m diagonal ops and D is the Hamming count;
+ *     if the hit came from kfmi_align_seeds at the same band with E <= w and
+ *     B + m <= n, then D <= E: a path with E edits drifts at most E diagonals
+ *     from its begin, so it lies in the band around c = B.  D < E is allowed:
+ *     E is the best over the bands around the seeds' origins, and the band
+ *     around B may hold a cheaper path that those do not.
+ *   What a record does not hold: affine gap costs, indels longer than the band
+ * and soft clipping.
+ *   Arguments, coverage, refusals.  The tables built on demand are those of
+ * kfmi_align_seeds; only the 2-bit text of the text jump's tables is read.
+ * Coverage: "task" and "task-mid", K = 1, 2, one device, the queries' ASCII
+ * rows on the device, reads of at most 256 bases.  KFMI_E_BAD_ARGUMENT: band >
+ * KFMI_ALIGN_MAX_BAND, C outside 1 .. KFMI_PATH_MAX_ENTRIES, an unknown
+ * `strands`, handles of another size; KFMI_E_NOT_IMPLEMENTED: the cases of
+ * kfmi_align_seeds.  A refused call writes nothing.  max_edits may be any value.
+ *   The kernel keeps three words per row and task in a device workspace that
+ * the call allocates and frees (KFMI_E_DEVICE_ALLOC when it does not fit), and
+ * launches in chunks of tasks so that the workspace stays under 1 GiB.
+ * kfmi_set_path_chunk(tasks) is a process-wide test knob: chunks of `tasks`
+ * tasks, rounded up to a multiple of 64, whatever the batch; 0 = by the cap.
+ * No result depends on it.
+ *   kfmi_last_timing: total, 0, the sum of the paths kernel's launches (ms);
+ * both are device time, so the workspace's allocation is in neither.
+ *   kfmi_align_paths_cpu: the same definition on the host as a plain full-band
+ * table and the walk (OpenMP, nthreads as for kfmi_search_cpu), on the text as
+ * ASCII and the handles' host arrays; no suffix array, no index, no device. */
+#define KFMI_PATH_EDITS_MASK  0x0000FFFFu   /* y bits 0-15: the path's edits D                         */
+#define KFMI_PATH_RUNS_SHIFT  16            /* y bits 16-27: the runs of the path (<= 2 D + 1)         */
+#define KFMI_PATH_RUNS_MASK   0x00000FFFu
+#define KFMI_PATH_OVERFLOW    0x80000000u   /* y bit 31: more than 2C runs, no word written            */
+#define KFMI_PATH_MAX_ENTRIES 32u
+int32_t kfmi_align_paths(void *index, void *queries, void *hits, void *paths, void *cigars,
+                         uint32_t strands, uint32_t band, uint32_t max_edits, uint32_t cigar_entries);
+int32_t kfmi_align_paths_cpu(const char *text, uint64_t n, void *queries, void *hits, void *paths, void *cigars,
+                             uint32_t strands, uint32_t band, uint32_t max_edits, uint32_t cigar_entries,
+                             int32_t nthreads);
+int32_t kfmi_set_path_chunk(uint64_t tasks);
 
 /* ---- walk trace (tests and diagnosis; not in the reference, not timed) -------
  * The fused forward task kernel ends a walk early through three shortcuts --

@@ -174,6 +174,44 @@ extern "C" int32_t kfmi_results_to_device(void* results)
   return KFMI_SUCCESS;
 }
 
+int32_t TextCall::open(kfmi_fmi_t* f, kfmi_qrys_t* q, std::initializer_list<const kfmi_res_t*> rs)
+{
+  lk = std::shared_lock<RwLock>(index_lock(f));
+  /* the copies the seed search covers, which the text jump builds its tables for, and the ASCII rows */
+  int32_t err = resident_single(f, q, rs, NEED_LANE_KERNELS | NEED_ASCII);
+  if (err) return err;
+  di = f->dev;
+  dq = q->dev;
+  if (dq->device != di->device || dq->num != q->num || dq->size != q->size) return KFMI_E_BAD_ARGUMENT;
+  err = search_lane(di->device, &l);
+  if (err) return err;
+  /* the text jump's tables, built here where the copy has none -- the path
+   * kfmi_set_jump(1) takes at a first search, whatever this thread's setting */
+  IdxArgs ix = idx_args(di);
+  err = use_jump(di, l.st, ix, 1u);
+  if (err) return err;
+  if (!ix.jsa) return KFMI_E_NOT_IMPLEMENTED;   /* the index failed the tables' exactness check */
+  jsa = ix.jsa;
+  split4 = split_for(8ull * di->bwtsize, LAY_INTER) == 4u ? 1u : 0u;
+  return KFMI_SUCCESS;
+}
+
+int32_t TextCall::begin()
+{
+  HIP_OK(hipEventRecord(l.ev[0], l.st));
+  HIP_OK(hipEventRecord(l.ev[1], l.st));
+  return KFMI_SUCCESS;
+}
+
+int32_t TextCall::finish()
+{
+  HIP_OK(hipEventRecord(l.ev[2], l.st));
+  const int32_t err = search_finish(l.st, l.ev, t_ms);
+  t_ms[0] = t_ms[2];   /* total, 0, the kernel: nothing is packed beforehand */
+  t_ms[1] = 0.0;
+  return err;
+}
+
 int32_t seed_score_call(void* index, void* queries, void* intervals, void* spans, void* hits, uint32_t max_seeds,
                         uint32_t strands, uint32_t max_occ, uint32_t band, uint32_t bound, SeedScoreLaunch launch)
 {
@@ -189,45 +227,27 @@ int32_t seed_score_call(void* index, void* queries, void* intervals, void* spans
   const uint64_t tasks = (strands == KFMI_STRAND_BOTH ? 2u : 1u) * q->num;
   if (ri->num != max_seeds * tasks || rs->num != max_seeds * tasks || rh->num != tasks) return KFMI_E_BAD_ARGUMENT;
   if (q->size < 1 || q->size > 256) return KFMI_E_BAD_ARGUMENT;
-  DeviceGuard dg;
-  std::shared_lock<RwLock> lk(index_lock(f));
-  /* the copies the seed search covers, which the text jump builds its tables for, and the ASCII rows */
-  int32_t err = resident_single(f, q, {ri, rs, rh}, NEED_LANE_KERNELS | NEED_ASCII);
+  TextCall c;
+  int32_t err = c.open(f, q, {ri, rs, rh});
   if (err) return err;
-  kfmi_dev_index* di = f->dev;
-  kfmi_dev_queries* dq = q->dev;
-  if (dq->device != di->device || dq->num != q->num || dq->size != q->size) return KFMI_E_BAD_ARGUMENT;
-  SearchLane l;
-  err = search_lane(di->device, &l);
-  if (err) return err;
-  /* the text jump's tables, built here where the copy has none -- the path
-   * kfmi_set_jump(1) takes at a first search, whatever this thread's setting */
-  IdxArgs ix = idx_args(di);
-  err = use_jump(di, l.st, ix, 1u);
-  if (err) return err;
-  if (!ix.jsa) return KFMI_E_NOT_IMPLEMENTED;   /* the index failed the tables' exactness check */
   VerifyArgs a{};
-  a.ascii = dq->ascii;
+  a.ascii = c.dq->ascii;
   a.iv = reinterpret_cast<const uint2*>(ri->d_results);
   a.sp = reinterpret_cast<const uint2*>(rs->d_results);
   a.hits = reinterpret_cast<uint2*>(rh->d_results);
-  a.jsa = ix.jsa;
-  a.num = dq->num;
-  a.m = dq->size;
+  a.jsa = c.jsa;
+  a.num = c.dq->num;
+  a.m = c.dq->size;
   a.strands = strands;
   a.S = max_seeds;
-  a.rows = di->bwtsize;
+  a.rows = c.di->bwtsize;
   a.max_occ = max_occ;
   a.max_mism = bound;
-  a.split4 = split_for(8ull * di->bwtsize, LAY_INTER) == 4u ? 1u : 0u;
-  HIP_OK(hipEventRecord(l.ev[0], l.st));
-  HIP_OK(hipEventRecord(l.ev[1], l.st));
-  if (dq->num) HIP_OK(launch(a, band, l.st));
-  HIP_OK(hipEventRecord(l.ev[2], l.st));
-  err = search_finish(l.st, l.ev, t_ms);
-  t_ms[0] = t_ms[2];   /* total, 0, the kernel: nothing is packed beforehand */
-  t_ms[1] = 0.0;
-  return err;
+  a.split4 = c.split4;
+  err = c.begin();
+  if (err) return err;
+  if (c.dq->num) HIP_OK(launch(a, band, c.l.st));
+  return c.finish();
 }
 
 extern "C" int32_t kfmi_verify_seeds(void* index, void* queries, void* intervals, void* spans, void* hits,

@@ -176,6 +176,9 @@ def load() -> ctypes.CDLL:
         "kfmi_verify_seeds_cpu": (i32, [vp, u64, vp, u64, vp, vp, vp, vp, u32, u32, u32, u32, i32]),
         "kfmi_align_seeds": (i32, [vp, vp, vp, vp, vp, u32, u32, u32, u32, u32]),
         "kfmi_align_seeds_cpu": (i32, [vp, u64, vp, u64, vp, vp, vp, vp, u32, u32, u32, u32, u32, i32]),
+        "kfmi_align_paths": (i32, [vp, vp, vp, vp, vp, u32, u32, u32, u32]),
+        "kfmi_align_paths_cpu": (i32, [vp, u64, vp, vp, vp, vp, u32, u32, u32, u32, i32]),
+        "kfmi_set_path_chunk": (i32, [u64]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -1264,6 +1267,102 @@ def map_reads_array(index: Index, reads: np.ndarray, backend: str | None = None,
         iv.close()
         sp.close()
         hits.close()
+
+
+PATH_EDITS_MASK = 0x0000FFFF
+PATH_RUNS_SHIFT = 16
+PATH_RUNS_MASK = 0x00000FFF
+PATH_OVERFLOW = 0x80000000
+PATH_MAX_ENTRIES = 32
+CIGAR_OPS = {1: "I", 2: "D", 7: "=", 8: "X"}
+
+
+def align_paths(index: Index, queries: Queries, hits: Results, paths: Results, cigars: Results, strands: int, band: int,
+                max_edits: int, cigar_entries: int) -> None:
+    """kfmi_align_paths: the CIGAR and the end position of every task's
+    placement at the begin position word x of its entry of `hits` holds (as
+    align_seeds or verify_seeds leaves it on the device).  Entry t of `paths`
+    (ns * num entries): x = the end position or HIT_NONE, y = edits | runs <<
+    PATH_RUNS_SHIFT | PATH_OVERFLOW.  `cigars` (ns * num * cigar_entries
+    entries): task t's 2 * cigar_entries words, run r = len << 4 | op with
+    BAM's codes I 1, D 2, = 7, X 8."""
+    _check(load().kfmi_align_paths(index.ptr, queries.ptr, hits.ptr, paths.ptr, cigars.ptr, int(strands), int(band),
+                                   int(max_edits), int(cigar_entries)), "kfmi_align_paths")
+
+
+def align_paths_cpu(text, queries: Queries, hits: Results, paths: Results, cigars: Results, strands: int, band: int,
+                    max_edits: int, cigar_entries: int, nthreads: int = 0) -> None:
+    """kfmi_align_paths_cpu: the same records on the host, from the text (bytes
+    or uint8 array of n bases) and the handles' host arrays."""
+    t = np.ascontiguousarray(np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text,
+                             dtype=np.uint8)
+    _check(load().kfmi_align_paths_cpu(t.ctypes.data_as(ctypes.c_void_p), t.size, queries.ptr, hits.ptr, paths.ptr,
+                                       cigars.ptr, int(strands), int(band), int(max_edits), int(cigar_entries),
+                                       int(nthreads)), "kfmi_align_paths_cpu")
+
+
+def set_path_chunk(tasks: int) -> None:
+    """kfmi_set_path_chunk (process-wide test knob): align_paths launches chunks
+    of `tasks` tasks, rounded up to a multiple of 64; 0 = by the workspace cap."""
+    _check(load().kfmi_set_path_chunk(int(tasks)), "kfmi_set_path_chunk")
+
+
+def decode_paths(paths: np.ndarray):
+    """(end int64 with -1 for none, edits, runs, overflow) of uint32 [T, 2] path records."""
+    p = np.asarray(paths, dtype=np.uint32).reshape(-1, 2)
+    x, y = p[:, 0].astype(np.int64), p[:, 1].astype(np.int64)
+    none = x == HIT_NONE
+    return (np.where(none, -1, x), np.where(none, 0, y & PATH_EDITS_MASK),
+            np.where(none, 0, (y >> PATH_RUNS_SHIFT) & PATH_RUNS_MASK), ((y & PATH_OVERFLOW) != 0) & ~none)
+
+
+def cigar_strings(paths: np.ndarray, cigars: np.ndarray, cigar_entries: int) -> list:
+    """One string per task, "57=1X42="-style, from the records of align_paths:
+    "*" where the task has no path or its path overflowed its words."""
+    _, _, runs, over = decode_paths(paths)
+    words = np.asarray(cigars, dtype=np.uint32).reshape(runs.size, 2 * int(cigar_entries))
+    out = []
+    for t in range(runs.size):
+        if runs[t] == 0 or over[t]:
+            out.append("*")
+        else:
+            out.append("".join("%d%s" % (int(v) >> 4, CIGAR_OPS[int(v) & 15]) for v in words[t, :runs[t]]))
+    return out
+
+
+def map_paths_array(index: Index, reads: np.ndarray, backend: str | None = None, max_seeds: int = 4,
+                    strands: int = STRAND_BOTH, max_occ: int = 8, band: int = 3, max_edits: int | None = None,
+                    cigar_entries: int = 8):
+    """Upload, seed search, align_seeds and align_paths of uint8 [N, m] reads
+    in one call, all on the device: how each task lies on the text.  Returns
+    (begin, end, edits, cigar): int64 arrays of ns * N tasks (BOTH: task 2q +
+    strand) with -1 / -1 / 0 where the task is not placed, and a list of CIGAR
+    strings ("*" where there is none).  edits are those of the path at the
+    reported begin position, bounded by max_edits (None: no bound)."""
+    n, s = reads.shape[0], int(max_seeds)
+    ns = _strand_count(strands)
+    me = 0xFFFFFFFF if max_edits is None else int(max_edits)
+    c = int(cigar_entries)
+    if backend:
+        set_backend(backend)
+    q = Queries.from_array(reads)
+    iv, sp = Results.alloc(max(s, 0) * ns * n), Results.alloc(max(s, 0) * ns * n)
+    hits, paths, cig = Results.alloc(ns * n), Results.alloc(ns * n), Results.alloc(max(c, 0) * ns * n)
+    try:
+        transfer_to_gpu(index, q, iv)
+        for h in (sp, hits, paths, cig):
+            transfer_to_gpu(index, None, h)
+        search_seeds(index, q, iv, sp, s, strands)
+        align_seeds(index, q, iv, sp, hits, s, strands, max_occ, band, me)
+        align_paths(index, q, hits, paths, cig, strands, band, me, c)
+        for h in (hits, paths, cig):
+            transfer_to_cpu(h)
+        end, edits, _, _ = decode_paths(paths.array())
+        begin = np.where(end < 0, -1, hits.array().reshape(-1, 2)[:, 0].astype(np.int64))
+        return begin, end, edits, cigar_strings(paths.array(), cig.array(), c)
+    finally:
+        for h in (q, iv, sp, hits, paths, cig):
+            h.close()
 
 
 def env_int(name: str, default: int) -> int:
