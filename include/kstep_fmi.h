@@ -916,6 +916,127 @@ int32_t kfmi_align_paths_cpu(const char *text, uint64_t n, void *queries, void *
                              int32_t nthreads);
 int32_t kfmi_set_path_chunk(uint64_t tasks);
 
+/* ---- place windows / pairs (not in the reference, which stops at intervals) --
+ * The two steps a paired-end mapper takes after the single-end pass: place a
+ * read inside a text window without any seed, and choose per pair of reads the
+ * concordant combination of placements.  Three calls: kfmi_mate_windows forms
+ * the window each task's mate implies, kfmi_place_windows places every task in
+ * its window, kfmi_pair_hits chooses.  Every record has the `hits` format of
+ * "verify seeds" (x, y; KFMI_HIT_NONE, KFMI_HIT_MULTI), so kfmi_align_paths
+ * takes each of them as it is.
+ *
+ *   kfmi_place_windows.  Tasks, their order and the strand modes are those of
+ * kfmi_align_seeds (ns = 2 for BOTH, task t = 2q + strand; a REV task is the
+ * read P').  `windows` and `hits` are results handles of exactly ns * num
+ * entries.  Entry t of `windows` is (lo, len) and names the begin positions lo,
+ * lo + 1, .., lo + len - 1; len = 0 means the task places nothing.  A `windows`
+ * handle may be caller-filled and sent up with kfmi_results_to_device, or left
+ * on the device by kfmi_mate_windows.  With n the text's length and m the read
+ * length:
+ *   Table.  A(i, j), 0 <= i <= m, 0 <= j <= n, is the least number of unit-cost
+ * edits that align P[i .. m) to text beginning at j and ending anywhere at or
+ * before n: A(m, j) = 0 for every j, A(i, n) = m - i, and for i < m, j < n the
+ * minimum of
+ *     A(i+1, j+1) + [base2index(P[i]) != code(T[j])],
+ *     A(i+1, j)   + 1      (a read base with no text base),
+ *     A(i,   j+1) + 1      (a text base skipped).
+ * e(b) = A(0, b) for 0 <= b <= n; in particular e(n) = m and e(b) <= m.  There
+ * is no band: the path drifts as far as its edits allow, so an indel of any
+ * length up to max_edits is found.
+ *   Record.  The begin positions of task t are the b with lo <= b < lo + len
+ * and b <= n.  E is the least e(b) over them, B_min and B_max the smallest and
+ * the largest b that attain E.  If a begin position exists and E <= max_edits:
+ * x = B_min, y = E | KFMI_HIT_MULTI iff B_max > B_min.  Otherwise x =
+ * KFMI_HIT_NONE, y = 0.  Bits 20 to 31 of y are 0 -- there are no candidates to
+ * count.  Every entry of `hits` is written, and nothing depends on evaluation
+ * order.
+ *   Scan bound.  A placement with e edits that begins at b uses at most m + e
+ * text bases, so with K = min(max_edits, m) the call may treat the text as
+ * ending at min(n, lo + len - 1 + m + K): every e(b) <= max_edits keeps its
+ * value and every other one stays above max_edits, so no record changes.  The
+ * cost of a task is (len + m + K) columns of m cells, whatever n is.
+ *   Into kfmi_align_paths.  That call reads word x alone and needs its band
+ * given explicitly; a placement found here whose path drifts more than that
+ * band from its begin position is then simply not reproduced there (its record
+ * is the banded table's, or no path).  For a record with E <= band and B + m <=
+ * n the path's edits D satisfy D <= E, by the argument given there.
+ *   Refusals.  len > KFMI_WINDOW_MAX_LEN in any entry: KFMI_E_BAD_ARGUMENT and
+ * nothing is written.  kfmi_place_windows decides that on the device -- a check
+ * kernel raises a flag that the placing kernel reads before it writes and the
+ * host reads after the call's one wait -- so windows left on the device never
+ * visit the host; kfmi_place_windows_cpu checks the host array first.  Unknown
+ * `strands`, handles of another size, reads over 256 bases:
+ * KFMI_E_BAD_ARGUMENT.  Coverage and KFMI_E_NOT_IMPLEMENTED are exactly those
+ * of kfmi_align_seeds ("task" and "task-mid", K = 1, 2, one device, the reads'
+ * ASCII rows on the device), the tables built on demand too; only the 2-bit
+ * text of the text jump's tables is read.  max_edits may be any value.  A
+ * refused call writes nothing.  kfmi_last_timing: total, 0, the window kernel.
+ *   kfmi_place_windows_cpu: the same definition on the host as a plain table
+ * per task (OpenMP, nthreads as for kfmi_search_cpu) on the text as ASCII and
+ * the handles' host arrays; no suffix array, no index, no device.
+ *
+ *   kfmi_mate_windows.  Reads 2p and 2p + 1 are mates (interleaved, as in
+ * interleaved FASTQ), all of one length m = read_len, and `hits` and `windows`
+ * have 2 * num entries in BOTH order, num even.  The layout is forward-reverse:
+ * a FWD task that begins at B_f and a REV task that begins at B_r form the
+ * fragment frag = B_r + m - B_f, and the two are concordant iff B_r >= B_f and
+ * min_frag <= frag <= max_frag.  The mate task of t = 2q + s is u = 2 (q ^ 1) +
+ * (s ^ 1) = t ^ 3.  If hits[u].x is KFMI_HIT_NONE the window of t is (0, 0).
+ * Otherwise, with B_u = hits[u].x, the begin positions concordant with it are
+ *     [B_u + min_frag - m, B_u + max_frag - m]   when s is REV,
+ *     [B_u + m - max_frag, B_u + m - min_frag]   when s is FWD,
+ * clipped to [0, n] in 64-bit signed arithmetic; (0, 0) if nothing is left,
+ * else (lo, hi - lo + 1).  mode 0 also writes (0, 0) when the task's own hit
+ * exists and is concordant with hits[u] already, so that only the tasks that
+ * need it are rescued; mode 1 writes the window regardless.  Required: 1 <= m
+ * <= 256, m <= min_frag <= max_frag, max_frag - min_frag + 1 <=
+ * KFMI_WINDOW_MAX_LEN, mode 0 or 1, an entry count that is a multiple of 4 and
+ * equal in both handles -- else KFMI_E_BAD_ARGUMENT.  n comes from the index;
+ * kfmi_mate_windows_cpu takes it as an argument and works on the host arrays.
+ *
+ *   kfmi_pair_hits.  `hits` (each task's own record), `rescued` (the records
+ * kfmi_place_windows formed in the mate windows) and `paired` have 2 * num
+ * entries in BOTH order.  Per pair p with reads a = 2p and b = 2p + 1:
+ * orientation k = 0 is (f, r) = (task(a, FWD), task(b, REV)), k = 1 is
+ * (task(b, FWD), task(a, REV)); each side takes its own hit (source 0) or its
+ * rescued record (source 1).  A combination (k, s_f, s_r) is admissible iff
+ * both records exist, they are concordant and s_f + s_r <= 1 (a rescued record
+ * is anchored on the mate's own hit, so two rescued records anchor nothing).
+ * The admissible combination with the lexicographically least (E_f + E_r, s_f +
+ * s_r, k, B_f, B_r, s_f) is chosen -- the last key only separates two
+ * combinations that reach the same two places with the sources swapped.  Then
+ * paired[f] and paired[r] are x = B, y = E | the source record's KFMI_HIT_MULTI
+ * bit | KFMI_PAIR_PROPER | KFMI_PAIR_RESCUED iff that side's source is 1, and
+ * the pair's other two tasks are (KFMI_HIT_NONE, 0).  With no admissible
+ * combination each read alone keeps the least (E, strand) of its own two hits,
+ * without KFMI_PAIR_PROPER; its other task, or both if it has no hit, is
+ * (KFMI_HIT_NONE, 0).  Rescued records are never used unpaired.  Bits 20 to 31
+ * of y are 0.  Every entry is written; nothing depends on evaluation order.
+ * kfmi_align_paths(.., paired, .., KFMI_STRAND_BOTH, ..) then gives the CIGARs
+ * of exactly the chosen tasks.  Arguments as for kfmi_mate_windows; three
+ * distinct handles of one size.
+ *   Both record calls run on the device the index is on, refuse what
+ * kfmi_align_seeds refuses (KFMI_E_NOT_IMPLEMENTED: coop and AltCounters
+ * backends, K = 3 / 4, device groups; KFMI_E_NOT_ON_DEVICE) and set
+ * kfmi_last_timing to total, 0, their kernel.
+ *   What the three calls do not do: reads of unequal length within a pair,
+ * layouts other than forward-reverse, affine gaps, soft clipping, SAM output. */
+#define KFMI_WINDOW_MAX_LEN 4096u
+#define KFMI_PAIR_PROPER  0x00020000u   /* y bit 17: the record is one side of the pair's chosen combination */
+#define KFMI_PAIR_RESCUED 0x00040000u   /* y bit 18: that side is the record placed in the mate's window    */
+int32_t kfmi_place_windows(void *index, void *queries, void *windows, void *hits,
+                           uint32_t strands, uint32_t max_edits);
+int32_t kfmi_place_windows_cpu(const char *text, uint64_t n, void *queries, void *windows, void *hits,
+                               uint32_t strands, uint32_t max_edits, int32_t nthreads);
+int32_t kfmi_mate_windows(void *index, void *hits, void *windows, uint32_t read_len,
+                          uint32_t min_frag, uint32_t max_frag, uint32_t mode);
+int32_t kfmi_mate_windows_cpu(uint64_t n, void *hits, void *windows, uint32_t read_len,
+                              uint32_t min_frag, uint32_t max_frag, uint32_t mode);
+int32_t kfmi_pair_hits(void *index, void *hits, void *rescued, void *paired, uint32_t read_len,
+                       uint32_t min_frag, uint32_t max_frag);
+int32_t kfmi_pair_hits_cpu(void *hits, void *rescued, void *paired, uint32_t read_len,
+                           uint32_t min_frag, uint32_t max_frag);
+
 /* ---- walk trace (tests and diagnosis; not in the reference, not timed) -------
  * The fused forward task kernel ends a walk early through three shortcuts --
  * the jump start, the skip table and the text jump (DESIGN.md 5a .. 5a''') --

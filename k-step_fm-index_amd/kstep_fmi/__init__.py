@@ -179,6 +179,12 @@ def load() -> ctypes.CDLL:
         "kfmi_align_paths": (i32, [vp, vp, vp, vp, vp, u32, u32, u32, u32]),
         "kfmi_align_paths_cpu": (i32, [vp, u64, vp, vp, vp, vp, u32, u32, u32, u32, i32]),
         "kfmi_set_path_chunk": (i32, [u64]),
+        "kfmi_place_windows": (i32, [vp, vp, vp, vp, u32, u32]),
+        "kfmi_place_windows_cpu": (i32, [vp, u64, vp, vp, vp, u32, u32, i32]),
+        "kfmi_mate_windows": (i32, [vp, vp, vp, u32, u32, u32, u32]),
+        "kfmi_mate_windows_cpu": (i32, [u64, vp, vp, u32, u32, u32, u32]),
+        "kfmi_pair_hits": (i32, [vp, vp, vp, vp, u32, u32, u32]),
+        "kfmi_pair_hits_cpu": (i32, [vp, vp, vp, u32, u32, u32]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -1362,6 +1368,122 @@ def map_paths_array(index: Index, reads: np.ndarray, backend: str | None = None,
         return begin, end, edits, cigar_strings(paths.array(), cig.array(), c)
     finally:
         for h in (q, iv, sp, hits, paths, cig):
+            h.close()
+
+
+WINDOW_MAX_LEN = 4096
+PAIR_PROPER = 0x00020000
+PAIR_RESCUED = 0x00040000
+
+
+def place_windows(index: Index, queries: Queries, windows: Results, hits: Results, strands: int, max_edits: int) -> None:
+    """kfmi_place_windows: the best unbanded semi-global placement of every
+    task among the begin positions lo .. lo + len - 1 of entry t = (lo, len) of
+    `windows` (caller-filled and sent up with results_to_gpu, or as
+    mate_windows leaves it on the device).  Entry t of `hits`: x = the smallest
+    begin position of a best placement or HIT_NONE, y = edits | HIT_MULTI."""
+    _check(load().kfmi_place_windows(index.ptr, queries.ptr, windows.ptr, hits.ptr, int(strands), int(max_edits)),
+           "kfmi_place_windows")
+
+
+def place_windows_cpu(text, queries: Queries, windows: Results, hits: Results, strands: int, max_edits: int,
+                      nthreads: int = 0) -> None:
+    """kfmi_place_windows_cpu: the same records on the host, from the text
+    (bytes or uint8 array of n bases) and the handles' host arrays."""
+    t = np.ascontiguousarray(np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text,
+                             dtype=np.uint8)
+    _check(load().kfmi_place_windows_cpu(t.ctypes.data_as(ctypes.c_void_p), t.size, queries.ptr, windows.ptr, hits.ptr,
+                                         int(strands), int(max_edits), int(nthreads)), "kfmi_place_windows_cpu")
+
+
+def mate_windows(index: Index, hits: Results, windows: Results, read_len: int, min_frag: int, max_frag: int,
+                 mode: int = 0) -> None:
+    """kfmi_mate_windows: entry t of `windows` (2 * num entries, BOTH order,
+    reads 2p and 2p + 1 mates) = the begin positions concordant with the hit of
+    t's mate task t ^ 3, or (0, 0).  mode 0 leaves out tasks whose own hit is
+    concordant already; mode 1 writes every window."""
+    _check(load().kfmi_mate_windows(index.ptr, hits.ptr, windows.ptr, int(read_len), int(min_frag), int(max_frag),
+                                    int(mode)), "kfmi_mate_windows")
+
+
+def mate_windows_cpu(n: int, hits: Results, windows: Results, read_len: int, min_frag: int, max_frag: int,
+                     mode: int = 0) -> None:
+    """kfmi_mate_windows_cpu: the same windows on the host arrays, for a text of n bases."""
+    _check(load().kfmi_mate_windows_cpu(int(n), hits.ptr, windows.ptr, int(read_len), int(min_frag), int(max_frag),
+                                        int(mode)), "kfmi_mate_windows_cpu")
+
+
+def pair_hits(index: Index, hits: Results, rescued: Results, paired: Results, read_len: int, min_frag: int,
+              max_frag: int) -> None:
+    """kfmi_pair_hits: per pair the concordant combination of own hits and
+    rescued records with the fewest edits; `paired` holds one placement per
+    read in the hits format, y | PAIR_PROPER | PAIR_RESCUED."""
+    _check(load().kfmi_pair_hits(index.ptr, hits.ptr, rescued.ptr, paired.ptr, int(read_len), int(min_frag),
+                                 int(max_frag)), "kfmi_pair_hits")
+
+
+def pair_hits_cpu(hits: Results, rescued: Results, paired: Results, read_len: int, min_frag: int, max_frag: int) -> None:
+    """kfmi_pair_hits_cpu: the same choice on the host arrays."""
+    _check(load().kfmi_pair_hits_cpu(hits.ptr, rescued.ptr, paired.ptr, int(read_len), int(min_frag), int(max_frag)),
+           "kfmi_pair_hits_cpu")
+
+
+def decode_pairs(paired: np.ndarray):
+    """(begin int64 with -1 for none, edits, multi, proper, rescued) of uint32 [T, 2] records of pair_hits."""
+    h = np.asarray(paired, dtype=np.uint32).reshape(-1, 2)
+    x, y = h[:, 0].astype(np.int64), h[:, 1].astype(np.int64)
+    none = x == HIT_NONE
+    return (np.where(none, -1, x), np.where(none, 0, y & HIT_MISM_MASK), ((y & HIT_MULTI) != 0) & ~none,
+            ((y & PAIR_PROPER) != 0) & ~none, ((y & PAIR_RESCUED) != 0) & ~none)
+
+
+def map_pairs_array(index: Index, reads: np.ndarray, min_frag: int, max_frag: int, backend: str | None = None,
+                    max_seeds: int = 4, max_occ: int = 8, band: int = 3, max_edits: int | None = None,
+                    cigar_entries: int = 8, mode: int = 0):
+    """Upload, seed search, align_seeds, mate_windows, place_windows, pair_hits
+    and align_paths of uint8 [N, m] interleaved mates (reads 2p and 2p + 1) in
+    one call, all on the device.  Returns per read (begin, end, strand, edits,
+    flags, cigar): int64 arrays of N entries -- begin / end -1, strand -1 and
+    edits 0 where the read is not placed; strand 0 = as written, 1 = reverse
+    complement; flags = the PAIR_PROPER / PAIR_RESCUED / HIT_MULTI bits of the
+    chosen record -- and a list of CIGAR strings ("*" where the read is not
+    placed, or where its rescued placement drifts out of `band`).  edits are
+    those of the chosen placement, bounded by max_edits (None: no bound)."""
+    n, s, m = reads.shape[0], int(max_seeds), reads.shape[1]
+    me = 0xFFFFFFFF if max_edits is None else int(max_edits)
+    c = int(cigar_entries)
+    if backend:
+        set_backend(backend)
+    q = Queries.from_array(reads)
+    iv, sp = Results.alloc(max(s, 0) * 2 * n), Results.alloc(max(s, 0) * 2 * n)
+    hits, win, resc, paired, paths = (Results.alloc(2 * n) for _ in range(5))
+    cig = Results.alloc(max(c, 0) * 2 * n)
+    try:
+        transfer_to_gpu(index, q, iv)
+        for h in (sp, hits, win, resc, paired, paths, cig):
+            transfer_to_gpu(index, None, h)
+        search_seeds(index, q, iv, sp, s, STRAND_BOTH)
+        align_seeds(index, q, iv, sp, hits, s, STRAND_BOTH, max_occ, band, me)
+        mate_windows(index, hits, win, m, min_frag, max_frag, mode)
+        place_windows(index, q, win, resc, STRAND_BOTH, me)
+        pair_hits(index, hits, resc, paired, m, min_frag, max_frag)
+        align_paths(index, q, paired, paths, cig, STRAND_BOTH, band, me, c)
+        for h in (paired, paths, cig):
+            transfer_to_cpu(h)
+        b, e, multi, proper, rescued = decode_pairs(paired.array())
+        end, _, _, _ = decode_paths(paths.array())
+        cs = cigar_strings(paths.array(), cig.array(), c)
+        b, e, end = b.reshape(n, 2), e.reshape(n, 2), end.reshape(n, 2)
+        y = paired.array().reshape(n, 2, 2)[:, :, 1].astype(np.int64)
+        strand = np.where(b[:, 0] >= 0, 0, np.where(b[:, 1] >= 0, 1, -1))
+        k = np.maximum(strand, 0)
+        r = np.arange(n)
+        placed = strand >= 0
+        flags = np.where(placed, y[r, k] & (PAIR_PROPER | PAIR_RESCUED | HIT_MULTI), 0)
+        return (b[r, k], np.where(placed, end[r, k], -1), strand, e[r, k], flags,
+                [cs[2 * i + int(k[i])] if placed[i] else "*" for i in range(n)])
+    finally:
+        for h in (q, iv, sp, hits, win, resc, paired, paths, cig):
             h.close()
 
 
