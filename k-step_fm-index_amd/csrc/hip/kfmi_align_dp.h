@@ -58,13 +58,16 @@ KFMI_DP_FN uint32_t even_bits(uint32_t x)
   return (x | (x >> 8)) & 0x0000FFFFu;
 }
 
-/* Row m of one candidate.  cw: the read's code words; tx: the stream words from
- * the one that holds base off - w of a stream with 16 bases in front (tx[j] is
- * word (off + 16 - w) / 16 + j - 1 of the stream, 0 where that is no word of the
- * text); sh = (off + 16 - w) % 16; low = max(w - off, 0). */
-template <int MAXW>
-KFMI_DP_FN void band_rows(const uint32_t (&cw)[MAXW], const uint32_t (&tx)[MAXW + 3], uint32_t m, uint32_t w,
-                          uint32_t sh, uint32_t low, uint32_t& vp_out, uint32_t& vn_out, uint32_t& s0_out)
+/* Row m of one candidate, every row handed to `keep(t - 1, vp, hp, eq)`, t = 1
+ * .. m in this order (kfmi_path_dp.h says what the three words are).  cw: the
+ * read's code words; tx: the stream words from the one that holds base off - w
+ * of a stream with 16 bases in front (tx[j] is word (off + 16 - w) / 16 + j - 1
+ * of the stream, 0 where that is no word of the text); sh = (off + 16 - w) % 16;
+ * low = max(w - off, 0). */
+template <int MAXW, class Keep>
+KFMI_DP_FN void band_rows_keep(const uint32_t (&cw)[MAXW], const uint32_t (&tx)[MAXW + 3], uint32_t m, uint32_t w,
+                               uint32_t sh, uint32_t low, Keep& keep, uint32_t& vp_out, uint32_t& vn_out,
+                               uint32_t& s0_out)
 {
   const uint32_t top = 1u << (2u * w), nw = (m + 15u) >> 4;
   uint32_t vp = 0u, vn = 0u, s0 = 0u;
@@ -92,11 +95,13 @@ KFMI_DP_FN void band_rows(const uint32_t (&cw)[MAXW], const uint32_t (&tx)[MAXW 
         const uint32_t pv = (vp >> 1) | top, mv = (vn >> 1) & ~top;
         const uint32_t xv = eq | mv;
         const uint32_t xh = (((eq & pv) + pv) ^ pv) | eq;
-        const uint32_t ph = ((mv | ~(xh | pv)) << 1) | 1u;
+        const uint32_t hp = mv | ~(xh | pv);
+        const uint32_t ph = (hp << 1) | 1u;
         const uint32_t mh = (pv & xh) << 1;
         s0 += 1u - (xv & 1u);
         vp = mh | ~(xv | ph);
         vn = ph & xv;
+        keep(16u * (uint32_t) j + r, vp, hp, eq);
         c >>= 2;
         a0 = (a0 >> 1) | (b0 << 31);
         b0 >>= 1;
@@ -108,6 +113,15 @@ KFMI_DP_FN void band_rows(const uint32_t (&cw)[MAXW], const uint32_t (&tx)[MAXW 
   vp_out = vp;
   vn_out = vn;
   s0_out = s0;
+}
+
+/* ... with no row kept: what kfmi_align_seeds scores a candidate with */
+template <int MAXW>
+KFMI_DP_FN void band_rows(const uint32_t (&cw)[MAXW], const uint32_t (&tx)[MAXW + 3], uint32_t m, uint32_t w,
+                          uint32_t sh, uint32_t low, uint32_t& vp_out, uint32_t& vn_out, uint32_t& s0_out)
+{
+  auto keep = [](uint32_t, uint32_t, uint32_t, uint32_t) {};
+  band_rows_keep<MAXW>(cw, tx, m, w, sh, low, keep, vp_out, vn_out, s0_out);
 }
 
 /* The task's running (E, B_min, B_max) updated with row m of one candidate:

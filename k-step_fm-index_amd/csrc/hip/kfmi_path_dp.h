@@ -1,7 +1,8 @@
 /*
  * kfmi_path_dp.h -- the alignment path of kfmi_align_paths on top of the banded
- * edit distance of kfmi_align_dp.h: the same row step with every row kept, and
- * the walk that reads the kept rows back.  Plain integer code, so the same text
+ * edit distance of kfmi_align_dp.h: what its row step hands to the keeper of
+ * band_rows_keep, the value of a cell of the last row, and the walk that reads
+ * the kept rows back.  Plain integer code, so the same text
  * compiles for the device and -- for checking it against the definition -- for
  * the host.  Orientation, bit order, text ends and the match planes are those
  * of kfmi_align_dp.h, with the band's centre c in place of the origin o.
@@ -39,59 +40,6 @@ namespace kfmi {
 
 /* BAM's codes of the four operations a path holds */
 enum : uint32_t { PATH_OP_I = 1u, PATH_OP_D = 2u, PATH_OP_EQ = 7u, PATH_OP_X = 8u };
-
-/* band_rows with every row handed to `keep(t - 1, vp, hp, eq)`, t = 1 .. m in
- * this order; cw, tx, sh and low as for band_rows, and the same last row out. */
-template <int MAXW, class Keep>
-KFMI_DP_FN void band_rows_keep(const uint32_t (&cw)[MAXW], const uint32_t (&tx)[MAXW + 3], uint32_t m, uint32_t w,
-                               uint32_t sh, uint32_t low, Keep& keep, uint32_t& vp_out, uint32_t& vn_out,
-                               uint32_t& s0_out)
-{
-  const uint32_t top = 1u << (2u * w), nw = (m + 15u) >> 4;
-  uint32_t vp = 0u, vn = 0u, s0 = 0u;
-  int32_t live = (int32_t) (0xFFFFFFFFu << low);   /* cells with a text base below them; one more per row */
-  uint32_t a0 = even_bits(tx[0]) | (even_bits(tx[1]) << 16), b0 = even_bits(tx[2]) | (even_bits(tx[3]) << 16);
-  uint32_t a1 = even_bits(tx[0] >> 1) | (even_bits(tx[1] >> 1) << 16);
-  uint32_t b1 = even_bits(tx[2] >> 1) | (even_bits(tx[3] >> 1) << 16);
-  a0 = (uint32_t) ((((uint64_t) b0 << 32) | a0) >> sh);
-  a1 = (uint32_t) ((((uint64_t) b1 << 32) | a1) >> sh);
-  b0 >>= sh;
-  b1 >>= sh;
-#pragma unroll
-  for (int j = 0; j < MAXW; ++j)
-    if ((uint32_t) j < nw) {
-      if (j > 0) {   /* 16 rows took 16 bases: the next word's go in above them */
-        b0 |= even_bits(tx[j + 3]) << (16u - sh);
-        b1 |= even_bits(tx[j + 3] >> 1) << (16u - sh);
-      }
-      uint32_t c = cw[j];
-      const uint32_t cnt = m - 16u * (uint32_t) j < 16u ? m - 16u * (uint32_t) j : 16u;
-#pragma unroll 1
-      for (uint32_t r = 0; r < cnt; ++r) {
-        const uint32_t p0 = 0u - (c & 1u), p1 = 0u - ((c >> 1) & 1u);
-        const uint32_t eq = ~((a0 ^ p0) | (a1 ^ p1)) & (uint32_t) live;
-        const uint32_t pv = (vp >> 1) | top, mv = (vn >> 1) & ~top;
-        const uint32_t xv = eq | mv;
-        const uint32_t xh = (((eq & pv) + pv) ^ pv) | eq;
-        const uint32_t hp = mv | ~(xh | pv);
-        const uint32_t ph = (hp << 1) | 1u;
-        const uint32_t mh = (pv & xh) << 1;
-        s0 += 1u - (xv & 1u);
-        vp = mh | ~(xv | ph);
-        vn = ph & xv;
-        keep(16u * (uint32_t) j + r, vp, hp, eq);
-        c >>= 2;
-        a0 = (a0 >> 1) | (b0 << 31);
-        b0 >>= 1;
-        a1 = (a1 >> 1) | (b1 << 31);
-        b1 >>= 1;
-        live >>= 1;
-      }
-    }
-  vp_out = vp;
-  vn_out = vn;
-  s0_out = s0;
-}
 
 /* the value of cell k of a row from its deltas; every cell below k is one the row step computed */
 KFMI_DP_FN uint32_t band_value(uint32_t vp, uint32_t vn, uint32_t s0, uint32_t k)

@@ -11,10 +11,9 @@
  * words per read (8 | 16) and on the staging (forward reads, or the strand
  * staging for REV and BOTH) alone.
  *
- * One lane per task.  The lane packs its whole read into registers with the
- * search's own packers -- rem = 0 whatever the index's K -- and walks its slots:
- * rows L, L + 1, .. below min(R, rows, L + max_occ), each row r a candidate
- * p = sa[r], origin o = p - start.  The read's code words and the text's word
+ * The frame is kfmi_text.h's: one lane per task, the read in registers, the
+ * slot and row generator of a seed walk.  Each row r is a candidate p = sa[r],
+ * origin o = p - start.  The read's code words and the text's word
  * stream share their bit order (the base at reversed index r at bits 2r), so the
  * window of origin o starts at bit 2 * (n - o - m) of the stream, takes
  * ceil(m / 16) + 1 dwords, and the Hamming distance is an XOR, a mask on the
@@ -22,92 +21,54 @@
  *
  * A round is wave-uniform.  Every lane issues the window loads of the candidate
  * it holds together with the sa load of its next row, then everything waits
- * once: a candidate costs about one round trip.  Where the tables are past the
- * translation reach (split_for(8 * rows, LAY_INTER) == 4, as for the jump's
- * gathers) a lane's loads go out under its 16-lane group's mask.  Every address
- * is in range before its load: rows below `rows`, window words clamped to the
- * stream's last word.
+ * once: a candidate costs about one round trip.  Every address is in range
+ * before its load: rows below `rows`, window words clamped to the stream's last
+ * word -- a window with no word in front, clamped and not zero-filled, so it is
+ * this file's and not kfmi_text.h's BandWindow.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <mutex>
-#include <shared_mutex>
 
-#include "../kfmi_internal.h"
-#include "kfmi_device.h"
-#include "kfmi_runtime.h"
-#include "kfmi_verify.h"
+#include "kfmi_text.h"
 
 namespace kfmi {
 
-/* STR: the strand staging (a.strands 2 = REV, 3 = BOTH: task 2q + strand), else forward reads. */
 template <int MAXW, bool STR>
 __global__ __launch_bounds__(256) void verify_kernel(VerifyArgs a)
 {
   extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
   uint32_t cw[MAXW];
-  if constexpr (STR) {
-    stage_strand_codes<MAXW>(a.ascii, a.num, a.m, stage, cw, a.strands);   /* whole block, before any exit */
-  } else {
-    uint32_t rc = 0;
-    stage_query_codes<MAXW>(a.ascii, a.num, a.m, stage, cw, 0u, rc);       /* whole block, before any exit */
-  }
-  const uint64_t t = (uint64_t) blockIdx.x * 256 + threadIdx.x;
-  if (t >= (STR && a.strands == 3u ? 2u : 1u) * a.num) return;
-  const uint32_t m = a.m, n = a.rows - 1u, nw = (m + 15u) >> 4;
-  const uint32_t* __restrict__ text = a.jsa + 2ull * a.rows;
+  uint64_t t;
+  if (!text_task<MAXW, STR>(a.ascii, a.num, a.m, a.strands, stage, cw, t)) return;
+  const uint32_t m = a.m, n = a.n, nw = (m + 15u) >> 4;
   const uint32_t wlast = (uint32_t) jump_text_words(n) - 1u;   /* the stream's last word */
   const uint2* __restrict__ ivt = a.iv + t * a.S;
   const uint2* __restrict__ spt = a.sp + t * a.S;
-  const int grp = (int) (threadIdx.x & 63u) / 16;
-  uint32_t s = 0, r = 0, rend = 0, start = 0;   /* the next slot, and the rows left of the current one */
-  uint32_t p = 0, pstart = 0;                   /* the candidate in hand: its sa value and its slot's start */
-  bool have = false;
+  const int grp = lane_group();
+  SeedRows k;
   uint32_t best_m = 0xFFFFFFFFu, best_o = 0xFFFFFFFFu, multi = 0u, scored = 0u;
   for (;;) {
-    /* lanes out of rows take their next slot; an ignored slot leaves them out of rows */
-    while (__ballot(r >= rend && s < a.S)) {
-      if (r >= rend && s < a.S) {
-        const uint2 lr = ivt[s], sl = spt[s];
-        ++s;
-        if (lr.y > lr.x && lr.x < a.rows && sl.y != 0u && (uint64_t) sl.x + sl.y <= m) {
-          const uint64_t cap = (uint64_t) lr.x + a.max_occ;
-          const uint32_t e = lr.y < a.rows ? lr.y : a.rows;
-          r = lr.x;
-          rend = cap < e ? (uint32_t) cap : e;
-          start = sl.x;
-        }
-      }
-    }
-    const bool more = r < rend;   /* r < rows */
-    if (!__ballot(more || have)) break;
-    const bool sc = have && p < a.rows && p >= pstart && (uint64_t) (p - pstart) + m <= n;
-    const uint32_t o = sc ? p - pstart : 0u;
+    k.refill(a, ivt, spt);
+    const bool more = k.more();
+    if (!__ballot(more || k.have)) break;
+    uint32_t o;
+    const bool sc = k.candidate(a, m, n, o);
     const uint32_t off = sc ? n - o - m : 0u;   /* the window starts at bit 2 * off of the stream */
     /* sc: n >= m, so wlast >= nw; a scored window ends inside the stream, the clamp never moves it */
     const uint32_t w0 = sc ? ((off >> 4) + nw <= wlast ? off >> 4 : wlast - nw) : 0u;
     const uint32_t sh = (off & 15u) * 2u;
     const uint32_t lim = sc ? nw + 1u : 0u;
-    const uint32_t* tp = text + w0;
+    const uint32_t* tp = a.text + w0;
     uint32_t tx[MAXW + 1];
 #pragma unroll
     for (int j = 0; j <= MAXW; ++j) tx[j] = 0u;
     uint32_t np = SKIP_NONE;
-    if (a.split4) {   /* wave-uniform: all of a lane's loads under its group's mask */
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-        if (grp == g) {
-#pragma unroll
-          for (int j = 0; j <= MAXW; ++j)
-            if ((uint32_t) j < lim) tx[j] = tp[j];
-          if (more) np = a.jsa[r];
-        }
-    } else {
+    under_group_mask(a.split4, grp, [&] {
 #pragma unroll
       for (int j = 0; j <= MAXW; ++j)
         if ((uint32_t) j < lim) tx[j] = tp[j];
-      if (more) np = a.jsa[r];
-    }
+      if (more) np = a.jsa[k.r];
+    });
     if (sc) {
       uint32_t mm = 0u;
 #pragma unroll
@@ -128,32 +89,19 @@ __global__ __launch_bounds__(256) void verify_kernel(VerifyArgs a)
         best_o = o < best_o ? o : best_o;
       }
     }
-    have = more;
-    if (more) {
-      p = np;
-      pstart = start;
-      ++r;
-    }
+    k.advance(np);
   }
-  const bool hit = scored != 0u && best_m <= a.max_mism;
+  const bool hit = scored != 0u && best_m <= a.bound;
   a.hits[t] = hit ? make_uint2(best_o, best_m | multi | (scored << KFMI_HIT_SCORED_SHIFT))
                   : make_uint2(KFMI_HIT_NONE, scored << KFMI_HIT_SCORED_SHIFT);
 }
 
 static hipError_t launch_verify(const VerifyArgs& a, uint32_t band, hipStream_t st)
 {
-  const bool str = a.strands != KFMI_STRAND_FWD;
   const uint64_t tasks = (a.strands == KFMI_STRAND_BOTH ? 2u : 1u) * a.num;
-  const dim3 grid((uint32_t) ((tasks + 255) / 256));
-  const size_t lds = 4 * (size_t) stage_slot_bytes(a.m);
-  if (a.m <= 128) {
-    if (str) hipLaunchKernelGGL((verify_kernel<8, true>), grid, dim3(256), lds, st, a);
-    else hipLaunchKernelGGL((verify_kernel<8, false>), grid, dim3(256), lds, st, a);
-  } else {
-    if (str) hipLaunchKernelGGL((verify_kernel<16, true>), grid, dim3(256), lds, st, a);
-    else hipLaunchKernelGGL((verify_kernel<16, false>), grid, dim3(256), lds, st, a);
-  }
-  return hipGetLastError();
+  return launch_text(a.m, a.strands, tasks, st, [&](auto W, auto S, dim3 grid, size_t lds) {
+    hipLaunchKernelGGL((verify_kernel<decltype(W)::value, decltype(S)::value>), grid, dim3(256), lds, st, a);
+  });
 }
 
 /* The host array of a transferred results handle copied to its device array:
@@ -172,6 +120,23 @@ extern "C" int32_t kfmi_results_to_device(void* results)
   HIP_OK(hipMemcpyAsync(r->d_results, r->h_results, 8ull * r->num, hipMemcpyHostToDevice, ctx->st));
   HIP_OK(hipStreamSynchronize(ctx->st));
   return KFMI_SUCCESS;
+}
+
+int32_t RecordCall::open(kfmi_fmi_t* f, std::initializer_list<const kfmi_res_t*> rs)
+{
+  lk = std::shared_lock<RwLock>(index_lock(f));
+  /* resident_single's refusals in its order, without reads */
+  if (f->grp) return KFMI_E_NOT_IMPLEMENTED;
+  for (const kfmi_res_t* r : rs)
+    if (r->grp) return KFMI_E_NOT_IMPLEMENTED;
+  if (!f->dev) return KFMI_E_NOT_ON_DEVICE;
+  for (const kfmi_res_t* r : rs)
+    if (!r->d_results) return KFMI_E_NOT_ON_DEVICE;
+  if (!lane_kernels(f->dev)) return KFMI_E_NOT_IMPLEMENTED;
+  di = f->dev;
+  for (const kfmi_res_t* r : rs)
+    if (r->d_device != di->device) return KFMI_E_BAD_ARGUMENT;
+  return search_lane(di->device, &l);
 }
 
 int32_t TextCall::open(kfmi_fmi_t* f, kfmi_qrys_t* q, std::initializer_list<const kfmi_res_t*> rs)
@@ -196,14 +161,14 @@ int32_t TextCall::open(kfmi_fmi_t* f, kfmi_qrys_t* q, std::initializer_list<cons
   return KFMI_SUCCESS;
 }
 
-int32_t TextCall::begin()
+int32_t RecordCall::begin()
 {
   HIP_OK(hipEventRecord(l.ev[0], l.st));
   HIP_OK(hipEventRecord(l.ev[1], l.st));
   return KFMI_SUCCESS;
 }
 
-int32_t TextCall::finish()
+int32_t RecordCall::finish()
 {
   HIP_OK(hipEventRecord(l.ev[2], l.st));
   const int32_t err = search_finish(l.st, l.ev, t_ms);
@@ -230,20 +195,15 @@ int32_t seed_score_call(void* index, void* queries, void* intervals, void* spans
   TextCall c;
   int32_t err = c.open(f, q, {ri, rs, rh});
   if (err) return err;
-  VerifyArgs a{};
-  a.ascii = c.dq->ascii;
+  VerifyArgs a{c.args(strands)};
   a.iv = reinterpret_cast<const uint2*>(ri->d_results);
   a.sp = reinterpret_cast<const uint2*>(rs->d_results);
   a.hits = reinterpret_cast<uint2*>(rh->d_results);
   a.jsa = c.jsa;
-  a.num = c.dq->num;
-  a.m = c.dq->size;
-  a.strands = strands;
   a.S = max_seeds;
   a.rows = c.di->bwtsize;
   a.max_occ = max_occ;
-  a.max_mism = bound;
-  a.split4 = c.split4;
+  a.bound = bound;
   err = c.begin();
   if (err) return err;
   if (c.dq->num) HIP_OK(launch(a, band, c.l.st));

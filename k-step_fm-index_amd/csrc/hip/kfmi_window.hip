@@ -5,17 +5,16 @@
  * chosen per pair (kstep_fmi.h section 2, "place windows / pairs"; DESIGN.md
  * 5l; not in the reference, which stops at intervals).
  *
- * window_kernel's frame is align_kernel's (kfmi_align.hip): one lane per task,
- * the read packed into registers by the search's own stagers with rem = 0 --
- * REV tasks get P' from the strand staging -- and the 2-bit text of the text
- * jump's flat tables, whose word stream holds text base n - 1 - g at bits 2 g.
+ * window_kernel's frame is kfmi_text.h's: one lane per task, the read in
+ * registers -- REV tasks get P' from the strand staging -- over the text's word
+ * stream, which holds text base n - 1 - g at bits 2 g.
  * A task has no candidates: it scans the text from its scan end T - 1 down to
  * the window's first position lo, which in the stream is the bases n - T up to
  * n - 1 - lo, consecutive dwords walked upwards.  Every load is one dword at
  * its own 4-byte alignment, never wider, with the next dword in flight while
  * the 16 bases of one are consumed; where the tables are past the translation
- * reach a lane's loads go out under its 16-lane group's mask, as in
- * align_kernel.  Every word index is at most (n - 1) / 16, inside the stream.
+ * reach a lane's loads go out under its 16-lane group's mask
+ * (word_at below).  Every word index is at most (n - 1) / 16, inside the stream.
  *
  * The score is the multi-word bit-vector column step of kfmi_window_dp.h with
  * the number of 32-cell words a compile-time constant (1, 2, 4 or 8 for reads
@@ -36,23 +35,17 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../kfmi_internal.h"
 #include "../kfmi_pairs.h"
-#include "kfmi_device.h"
-#include "kfmi_runtime.h"
-#include "kfmi_verify.h"
+#include "kfmi_text.h"
 #include "kfmi_window_dp.h"
 
 namespace kfmi {
 
-struct WindowArgs {
-  const uint8_t* __restrict__ ascii;   /* num reads of m bases */
+struct WindowArgs : TextArgs {
   const uint2* __restrict__ win;       /* one (lo, len) per task */
   uint2* __restrict__ hits;            /* one record per task */
-  const uint32_t* __restrict__ text;   /* the text's word stream */
   const uint32_t* __restrict__ flag;   /* raised by window_check_kernel: some len is too large */
-  uint64_t num;
-  uint32_t m, strands, n, max_edits, split4;
+  uint32_t max_edits;
 };
 
 __global__ __launch_bounds__(256) void window_check_kernel(const uint2* __restrict__ win, uint64_t tasks,
@@ -62,40 +55,31 @@ __global__ __launch_bounds__(256) void window_check_kernel(const uint2* __restri
   if (t < tasks && win[t].y > KFMI_WINDOW_MAX_LEN) *flag = 1u;   /* every writer writes the same value */
 }
 
-/* word x of the stream, under the lane's 16-lane group's mask where split4 (wave-uniform) says so */
-__device__ __forceinline__ uint32_t window_text_word(const uint32_t* __restrict__ text, uint32_t x, uint32_t split4,
-                                                     int grp)
-{
-  uint32_t v = 0u;
-  if (split4) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-      if (grp == q) v = text[x];
-  } else {
-    v = text[x];
-  }
-  return v;
-}
-
-/* NW: 32-cell words per column; MAXW: the stagers' code words (8 | 16); STR: the strand staging (a.strands 2 = REV,
- * 3 = BOTH: task 2q + strand), else forward reads. */
+/* NW: 32-cell words per column; MAXW: the stagers' code words (8 | 16); STR: the strand staging, else forward reads */
 template <int NW, int MAXW, bool STR>
 __global__ __launch_bounds__(256) void window_kernel(WindowArgs a)
 {
   extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
   uint32_t cw[MAXW];
-  if constexpr (STR) {
-    stage_strand_codes<MAXW>(a.ascii, a.num, a.m, stage, cw, a.strands);   /* whole block, before any exit */
-  } else {
-    uint32_t rc = 0;
-    stage_query_codes<MAXW>(a.ascii, a.num, a.m, stage, cw, 0u, rc);       /* whole block, before any exit */
-  }
-  const uint64_t t = (uint64_t) blockIdx.x * 256 + threadIdx.x;
-  if (t >= (STR && a.strands == 3u ? 2u : 1u) * a.num) return;
+  uint64_t t;
+  if (!text_task<MAXW, STR>(a.ascii, a.num, a.m, a.strands, stage, cw, t)) return;
   if (*a.flag) return;   /* a refused call writes nothing */
   const uint32_t m = a.m, n = a.n;
-  const uint32_t* __restrict__ text = a.text;
-  const int grp = (int) (threadIdx.x & 63u) / 16;
+  const int grp = lane_group();
+  /* Word x of the stream, under the lane's 16-lane group's mask where split4 (wave-uniform) says so.  The kernel's own
+   * text and not under_group_mask: its rolled loop of turns around this one load, once per 16 columns of a scan bound
+   * by integer issue, cost 7 % of the kernel's time at scale. */
+  auto word_at = [&](uint32_t x) {
+    uint32_t v = 0u;
+    if (a.split4) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        if (grp == q) v = a.text[x];
+    } else {
+      v = a.text[x];
+    }
+    return v;
+  };
   const uint2 wn = a.win[t];
   uint32_t hi_b = 0u, T = 0u;
   const int any = window_scan(n, wn.x, wn.y, m, a.max_edits, &hi_b, &T);
@@ -111,8 +95,8 @@ __global__ __launch_bounds__(256) void window_kernel(WindowArgs a)
     const uint32_t gend = n - wn.x;          /* one past gl */
     if (g < gend) {
       const uint32_t xl = (gend - 1u) >> 4;  /* the last word the scan reads: <= (n - 1) / 16 */
-      uint32_t word = window_text_word(text, g >> 4, a.split4, grp);
-      uint32_t next = (g >> 4) < xl ? window_text_word(text, (g >> 4) + 1u, a.split4, grp) : 0u;
+      uint32_t word = word_at(g >> 4);
+      uint32_t next = (g >> 4) < xl ? word_at((g >> 4) + 1u) : 0u;
       while (g < gend) {
         const uint32_t c = (word >> (2u * (g & 15u))) & 3u;
         score += (uint32_t) window_step<NW>(peq, pv, mv, m, c);
@@ -121,7 +105,7 @@ __global__ __launch_bounds__(256) void window_kernel(WindowArgs a)
         ++g;
         if ((g & 15u) == 0u && g < gend) {
           word = next;
-          if ((g >> 4) < xl) next = window_text_word(text, (g >> 4) + 1u, a.split4, grp);
+          if ((g >> 4) < xl) next = word_at((g >> 4) + 1u);
         }
       }
     }
@@ -131,22 +115,18 @@ __global__ __launch_bounds__(256) void window_kernel(WindowArgs a)
   a.hits[t] = rec;
 }
 
-template <int NW, int MAXW>
-static void launch_window_nw(const WindowArgs& a, dim3 grid, size_t lds, hipStream_t st)
-{
-  if (a.strands != KFMI_STRAND_FWD) hipLaunchKernelGGL((window_kernel<NW, MAXW, true>), grid, dim3(256), lds, st, a);
-  else hipLaunchKernelGGL((window_kernel<NW, MAXW, false>), grid, dim3(256), lds, st, a);
-}
-
 static hipError_t launch_window(const WindowArgs& a, uint64_t tasks, hipStream_t st)
 {
-  const dim3 grid((uint32_t) ((tasks + 255) / 256));
-  const size_t lds = 4 * (size_t) stage_slot_bytes(a.m);
-  if (a.m <= 32) launch_window_nw<1, 8>(a, grid, lds, st);
-  else if (a.m <= 64) launch_window_nw<2, 8>(a, grid, lds, st);
-  else if (a.m <= 128) launch_window_nw<4, 8>(a, grid, lds, st);
-  else launch_window_nw<8, 16>(a, grid, lds, st);
-  return hipGetLastError();
+  return launch_text(a.m, a.strands, tasks, st, [&](auto W, auto S, dim3 grid, size_t lds) {
+    auto cells = [&](auto NW) {
+      hipLaunchKernelGGL((window_kernel<decltype(NW)::value, decltype(W)::value, decltype(S)::value>), grid, dim3(256),
+                         lds, st, a);
+    };
+    if constexpr (decltype(W)::value == 16) cells(std::integral_constant<int, 8>{});
+    else if (a.m <= 32) cells(std::integral_constant<int, 1>{});
+    else if (a.m <= 64) cells(std::integral_constant<int, 2>{});
+    else cells(std::integral_constant<int, 4>{});
+  });
 }
 
 extern "C" int32_t kfmi_place_windows(void* index, void* queries, void* windows, void* hits, uint32_t strands,
@@ -168,39 +148,25 @@ extern "C" int32_t kfmi_place_windows(void* index, void* queries, void* windows,
     err = c.begin();
     return err ? err : c.finish();
   }
-  uint32_t* flag = nullptr;
-  if (hipMalloc((void**) &flag, sizeof(uint32_t)) != hipSuccess) {
-    (void) hipGetLastError();
-    return KFMI_E_DEVICE_ALLOC;
-  }
-  WindowArgs a{};
-  a.ascii = c.dq->ascii;
+  DeviceScratch flag;
+  if ((err = flag.alloc(sizeof(uint32_t)))) return err;
+  WindowArgs a{c.args(strands)};
   a.win = reinterpret_cast<const uint2*>(rw->d_results);
   a.hits = reinterpret_cast<uint2*>(rh->d_results);
-  a.text = c.jsa + 2ull * c.di->bwtsize;
-  a.flag = flag;
-  a.num = c.dq->num;
-  a.m = c.dq->size;
-  a.strands = strands;
-  a.n = c.di->bwtsize - 1u;
+  a.flag = flag.p;
   a.max_edits = max_edits;
-  a.split4 = c.split4;
   uint32_t raised = 0u;
-  hipError_t he = hipMemsetAsync(flag, 0, sizeof(uint32_t), c.l.st);
+  hipError_t he = hipMemsetAsync(flag.p, 0, sizeof(uint32_t), c.l.st);
   if (he == hipSuccess) {
     hipLaunchKernelGGL(window_check_kernel, dim3((uint32_t) ((tasks + 255) / 256)), dim3(256), 0, c.l.st, a.win, tasks,
-                       flag);
+                       flag.p);
     he = hipGetLastError();
   }
   err = c.begin();   /* the timing is the window kernel's */
   if (!err && he == hipSuccess) he = launch_window(a, tasks, c.l.st);
   if (!err) err = c.finish();   /* waits for whatever was queued */
-  if (!err && he == hipSuccess) he = hipMemcpy(&raised, flag, sizeof(uint32_t), hipMemcpyDeviceToHost);
-  (void) hipFree(flag);
-  if (he != hipSuccess) {
-    fprintf(stderr, "kstepfmi: window_kernel launch failed: %s\n", hipGetErrorString(he));
-    return KFMI_E_KERNEL;
-  }
+  if (!err && he == hipSuccess) he = hipMemcpy(&raised, flag.p, sizeof(uint32_t), hipMemcpyDeviceToHost);
+  err = launch_result(err, he, "window_kernel");
   if (err) return err;
   return raised ? KFMI_E_BAD_ARGUMENT : KFMI_SUCCESS;
 }
@@ -239,44 +205,6 @@ __global__ __launch_bounds__(256) void pair_kernel(const uint32_t* __restrict__ 
   op[0] = make_uint4(out[0], out[1], out[2], out[3]);
   op[1] = make_uint4(out[4], out[5], out[6], out[7]);
 }
-
-/* The host side of the two record calls: the index's lock and device, every handle on that device, the calling
- * thread's lane; the coverage is kfmi_align_seeds' so that a chain of calls is refused as one. */
-struct RecordCall {
-  DeviceGuard dg;
-  std::shared_lock<RwLock> lk;
-  kfmi_dev_index* di = nullptr;
-  SearchLane l;
-  int32_t open(kfmi_fmi_t* f, std::initializer_list<const kfmi_res_t*> rs)
-  {
-    lk = std::shared_lock<RwLock>(index_lock(f));
-    if (f->grp) return KFMI_E_NOT_IMPLEMENTED;
-    for (const kfmi_res_t* r : rs)
-      if (r->grp) return KFMI_E_NOT_IMPLEMENTED;
-    if (!f->dev) return KFMI_E_NOT_ON_DEVICE;
-    for (const kfmi_res_t* r : rs)
-      if (!r->d_results) return KFMI_E_NOT_ON_DEVICE;
-    if (!lane_kernels(f->dev)) return KFMI_E_NOT_IMPLEMENTED;
-    di = f->dev;
-    for (const kfmi_res_t* r : rs)
-      if (r->d_device != di->device) return KFMI_E_BAD_ARGUMENT;
-    return search_lane(di->device, &l);
-  }
-  int32_t begin()
-  {
-    HIP_OK(hipEventRecord(l.ev[0], l.st));
-    HIP_OK(hipEventRecord(l.ev[1], l.st));
-    return KFMI_SUCCESS;
-  }
-  int32_t finish()
-  {
-    HIP_OK(hipEventRecord(l.ev[2], l.st));
-    const int32_t err = search_finish(l.st, l.ev, t_ms);
-    t_ms[0] = t_ms[2];
-    t_ms[1] = 0.0;
-    return err;
-  }
-};
 
 extern "C" int32_t kfmi_mate_windows(void* index, void* hits, void* windows, uint32_t read_len, uint32_t min_frag,
                                      uint32_t max_frag, uint32_t mode)
