@@ -1037,6 +1037,101 @@ int32_t kfmi_pair_hits(void *index, void *hits, void *rescued, void *paired, uin
 int32_t kfmi_pair_hits_cpu(void *hits, void *rescued, void *paired, uint32_t read_len,
                            uint32_t min_frag, uint32_t max_frag);
 
+/* ---- second placement / mapping quality (not in the reference) ---------------
+ * How much worse a task's next-best place is than the one kfmi_align_seeds
+ * reported: the gap every consumer of a mapper filters on.  A second pass over
+ * the same candidates, because "second-best" has to mean "best outside the
+ * neighbourhood of the reported begin position" -- else the two seeds either
+ * side of one indel would count as two places (see KFMI_HIT_MULTI under "align
+ * seeds") -- and that position is known only after every candidate was scored.
+ *
+ *   kfmi_align_second.  The tasks and their order, the S = max_seeds slots per
+ * task, the strand modes, the handle sizes of `intervals` and `spans`, the
+ * ignored-slot forms, the candidates of a slot (rows L, L + 1, .. below min(R,
+ * rows, L + max_occ)), which candidates are scored, the table A(i, d) and w =
+ * band are those of "align seeds".
+ *   Handles.  `hits`: ns * num entries, of which only word x is read: X, the
+ * begin position, or KFMI_HIT_NONE; left on the device by kfmi_align_seeds or
+ * caller-filled through kfmi_results_to_device.  `second`: exactly ns * num
+ * entries; every entry is written, whatever it held.
+ *   Definition for task t with X != KFMI_HIT_NONE.  A pair (scored candidate
+ * with origin o, d in [-w, w]) whose cell (0, d) is valid begins at b = o + d.
+ * The pair is far iff |b - X| > 2w, in signed 64-bit arithmetic.  E2 is the
+ * least A(0, d) over the far pairs, B2_min and B2_max the smallest and the
+ * largest far b that attain E2.  `counted` is the number of scored candidates
+ * with |o - X| > w: exactly the candidates that can own a far cell; the others
+ * may be skipped without a dynamic programme.  TRUNC is set iff some slot of
+ * the task that is not ignored has min(R, rows) - L > max_occ, so that rows of
+ * the interval were never looked at.
+ *   Record.  If a far pair exists and E2 <= max_second: x = B2_min, y = E2 |
+ * KFMI_HIT_MULTI iff B2_max - B2_min > 2w | KFMI_SECOND_TRUNCATED iff TRUNC |
+ * counted << 20.  Otherwise x = KFMI_HIT_NONE, y = (KFMI_SECOND_TRUNCATED iff
+ * TRUNC) | counted << 20.  X = KFMI_HIT_NONE: the record is (KFMI_HIT_NONE, 0).
+ * KFMI_SECOND_TRUNCATED is y bit 19; bits 17 and 18 are the pair flags.
+ * Nothing depends on the evaluation order.
+ *   What then holds.  If `hits` came from kfmi_align_seeds with the same slots,
+ * max_occ and band, with record edits E, and max_second >= E:
+ *     E2 >= E wherever a second exists;
+ *     E2 = E  <=>  the hit carries KFMI_HIT_MULTI (B_max - B_min > 2w is the
+ *     same test, because X = B_min);
+ *     counted <= scored;
+ *     with band 0, E2 is the least Hamming count over origins != X.
+ *   Arguments, coverage, refusals, the tables built on demand and
+ * kfmi_last_timing (total, 0, this kernel) are exactly those of
+ * kfmi_align_seeds, with `hits` and `second` two more distinct handles on the
+ * index's device; band > KFMI_ALIGN_MAX_BAND is KFMI_E_BAD_ARGUMENT; max_second
+ * may be any value.  A refused call writes nothing.
+ *   What a second does not see: a place no seed slot leads to.  The greedy
+ * seed search gives an exactly matching read one seed, the whole read, so a
+ * near-copy of its locus never becomes a candidate.  Caller-filled slots of
+ * fixed-length pieces of the read (the binding's piece_seeds, built from
+ * kfmi_search / kfmi_search_strands and kfmi_results_to_device) close that.
+ *   kfmi_align_second_cpu: the same definition on the host as a plain full
+ * table per candidate, with the arguments of kfmi_align_seeds_cpu plus `second`
+ * and max_second; no index, no device.
+ *
+ *   kfmi_map_quality.  A streaming call on records alone.  `hits`, `second` and
+ * `quals` have ns * num entries each (an even number in BOTH mode), and every
+ * entry of `quals` is written.  For task t with hits[t] = (X, y) and E = y &
+ * KFMI_HIT_MISM_MASK:
+ *     X = KFMI_HIT_NONE: the record is (0, 0).
+ *     C is the least of: E2 of second[t] if its x != KFMI_HIT_NONE; in BOTH
+ *     mode only, the edits of hits[t ^ 1] if that record exists (the read's
+ *     other strand competes with it); max_second + 1.
+ *     gap = max(C - E, 0), except in BOTH mode when hits[t ^ 1] has the same
+ *     edits and t is the REV task: then gap = 0.  (Equal edits give both tasks
+ *     gap 0 already; the clause keeps the rule explicit.)  gap is formed in 64
+ *     bits and its word saturates at 2^32 - 1.
+ *     q = min(KFMI_MAPQ_MAX, KFMI_MAPQ_PER_EDIT * gap).
+ *     If second[t] carries KFMI_SECOND_TRUNCATED, or in BOTH mode second[t ^ 1]
+ *     does, q = min(q, KFMI_MAPQ_TRUNCATED).
+ *     Record: x = q, y = gap.
+ * The constants 60, 10 and 3 are this project's definition and no claim of
+ * calibration against any other mapper's mapping quality.
+ *   Refusals are those of kfmi_pair_hits: three distinct handles of one size on
+ * the index's device, an unknown `strands` or an odd size in BOTH mode is
+ * KFMI_E_BAD_ARGUMENT; KFMI_E_NOT_IMPLEMENTED for the coop and AltCounters
+ * backends, K = 3 / 4 and device groups; KFMI_E_NOT_ON_DEVICE.
+ * kfmi_last_timing: total, 0, the kernel.  kfmi_map_quality_cpu works on the
+ * handles' host arrays.
+ *   What neither call does: the quality of a pair (where the second-best
+ * combination matters, not only the second-best side), affine gaps, soft
+ * clipping, SAM text. */
+#define KFMI_SECOND_TRUNCATED 0x00080000u   /* y bit 19: a slot held more rows than max_occ looked at        */
+#define KFMI_MAPQ_MAX         60u
+#define KFMI_MAPQ_PER_EDIT    10u
+#define KFMI_MAPQ_TRUNCATED   3u
+int32_t kfmi_align_second(void *index, void *queries, void *intervals, void *spans, void *hits, void *second,
+                          uint32_t max_seeds, uint32_t strands, uint32_t max_occ,
+                          uint32_t band, uint32_t max_second);
+int32_t kfmi_align_second_cpu(const char *text, uint64_t n, const uint32_t *sa, uint64_t rows,
+                              void *queries, void *intervals, void *spans, void *hits, void *second,
+                              uint32_t max_seeds, uint32_t strands, uint32_t max_occ,
+                              uint32_t band, uint32_t max_second, int32_t nthreads);
+int32_t kfmi_map_quality(void *index, void *hits, void *second, void *quals,
+                         uint32_t strands, uint32_t max_second);
+int32_t kfmi_map_quality_cpu(void *hits, void *second, void *quals, uint32_t strands, uint32_t max_second);
+
 /* ---- walk trace (tests and diagnosis; not in the reference, not timed) -------
  * The fused forward task kernel ends a walk early through three shortcuts --
  * the jump start, the skip table and the text jump (DESIGN.md 5a .. 5a''') --

@@ -145,4 +145,25 @@ KFMI_DP_FN void band_fold(uint32_t vp, uint32_t vn, uint32_t s0, uint32_t w, uin
   }
 }
 
+/* ... leaving out the cells that begin within 2w of X, the begin position already reported (kfmi_align_second): the
+ * running (E2, B2_min, B2_max) over the far cells alone, |b - X| > 2w in signed 64-bit arithmetic. */
+KFMI_DP_FN void band_fold_far(uint32_t vp, uint32_t vn, uint32_t s0, uint32_t w, uint32_t o, uint32_t n, uint32_t X,
+                              uint32_t& E, uint32_t& bmin, uint32_t& bmax)
+{
+  uint32_t v = s0;
+#pragma unroll 1
+  for (uint32_t k = 0; k <= 2u * w; ++k) {
+    if (k) v += ((vp >> k) & 1u) - ((vn >> k) & 1u);
+    const int64_t b = (int64_t) o + w - k, dx = b - (int64_t) X;
+    if (b < 0 || b > (int64_t) n || (dx <= 2 * (int64_t) w && dx >= -2 * (int64_t) w)) continue;
+    if (v < E) {
+      E = v;
+      bmin = bmax = (uint32_t) b;
+    } else if (v == E) {
+      bmin = (uint32_t) b < bmin ? (uint32_t) b : bmin;
+      bmax = (uint32_t) b > bmax ? (uint32_t) b : bmax;
+    }
+  }
+}
+
 }  // namespace kfmi

@@ -185,6 +185,10 @@ def load() -> ctypes.CDLL:
         "kfmi_mate_windows_cpu": (i32, [u64, vp, vp, u32, u32, u32, u32]),
         "kfmi_pair_hits": (i32, [vp, vp, vp, vp, u32, u32, u32]),
         "kfmi_pair_hits_cpu": (i32, [vp, vp, vp, u32, u32, u32]),
+        "kfmi_align_second": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, u32]),
+        "kfmi_align_second_cpu": (i32, [vp, u64, vp, u64, vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, i32]),
+        "kfmi_map_quality": (i32, [vp, vp, vp, vp, u32, u32]),
+        "kfmi_map_quality_cpu": (i32, [vp, vp, vp, u32, u32]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -1218,9 +1222,109 @@ def decode_hits(hits: np.ndarray):
             y >> HIT_SCORED_SHIFT)
 
 
+SECOND_TRUNCATED = 0x00080000
+MAPQ_MAX, MAPQ_PER_EDIT, MAPQ_TRUNCATED = 60, 10, 3
+
+
+def align_second(index: Index, queries: Queries, intervals: Results, spans: Results, hits: Results, second: Results,
+                 max_seeds: int, strands: int, max_occ: int, band: int, max_second: int) -> None:
+    """kfmi_align_second: over the candidates of align_seeds, the best banded
+    placement that begins more than 2 * band from word x of each task's hit.
+    Entry t of `second` (ns * num entries, on the device): x = its smallest
+    begin position or HIT_NONE, y = edits | HIT_MULTI | SECOND_TRUNCATED (a slot
+    held more rows than max_occ) | counted << HIT_SCORED_SHIFT."""
+    _check(load().kfmi_align_second(index.ptr, queries.ptr, intervals.ptr, spans.ptr, hits.ptr, second.ptr,
+                                    int(max_seeds), int(strands), int(max_occ), int(band), int(max_second)),
+           "kfmi_align_second")
+
+
+def align_second_cpu(text, sa: np.ndarray, queries: Queries, intervals: Results, spans: Results, hits: Results,
+                     second: Results, max_seeds: int, strands: int, max_occ: int, band: int, max_second: int,
+                     nthreads: int = 0) -> None:
+    """kfmi_align_second_cpu: the same records on the host, with the arguments of align_seeds_cpu."""
+    t = np.ascontiguousarray(np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text,
+                             dtype=np.uint8)
+    sa = np.ascontiguousarray(sa, dtype=np.uint32)
+    _check(load().kfmi_align_second_cpu(t.ctypes.data_as(ctypes.c_void_p), t.size, sa.ctypes.data_as(ctypes.c_void_p),
+                                        sa.size, queries.ptr, intervals.ptr, spans.ptr, hits.ptr, second.ptr,
+                                        int(max_seeds), int(strands), int(max_occ), int(band), int(max_second),
+                                        int(nthreads)), "kfmi_align_second_cpu")
+
+
+def map_quality(index: Index, hits: Results, second: Results, quals: Results, strands: int, max_second: int) -> None:
+    """kfmi_map_quality: entry t of `quals` is x = the quality min(MAPQ_MAX,
+    MAPQ_PER_EDIT * gap), at most MAPQ_TRUNCATED under SECOND_TRUNCATED, and
+    y = gap, the edits between the task's hit and the best of its second, its
+    read's other strand (STRAND_BOTH) and max_second + 1."""
+    _check(load().kfmi_map_quality(index.ptr, hits.ptr, second.ptr, quals.ptr, int(strands), int(max_second)),
+           "kfmi_map_quality")
+
+
+def map_quality_cpu(hits: Results, second: Results, quals: Results, strands: int, max_second: int) -> None:
+    """kfmi_map_quality_cpu: the same records from the handles' host arrays."""
+    _check(load().kfmi_map_quality_cpu(hits.ptr, second.ptr, quals.ptr, int(strands), int(max_second)),
+           "kfmi_map_quality_cpu")
+
+
+def decode_second(second: np.ndarray):
+    """(begin int64 with -1 for none, edits, multi, truncated, counted) of uint32 [T, 2] second records."""
+    h = np.asarray(second, dtype=np.uint32).reshape(-1, 2)
+    x, y = h[:, 0].astype(np.int64), h[:, 1].astype(np.int64)
+    none = x == HIT_NONE
+    return (np.where(none, -1, x), np.where(none, 0, y & HIT_MISM_MASK), ((y & HIT_MULTI) != 0) & ~none,
+            (y & SECOND_TRUNCATED) != 0, y >> HIT_SCORED_SHIFT)
+
+
+def piece_bounds(m: int, pieces: int) -> list:
+    """(start, len) of the `pieces` equal consecutive pieces of an m-base read; the last takes the remainder."""
+    s, ln = int(pieces), int(m) // int(pieces)
+    return [(j * ln, ln if j < s - 1 else int(m) - (s - 1) * ln) for j in range(s)]
+
+
+def piece_seeds(index: Index, reads: np.ndarray, pieces: int, strands: int, intervals: Results | None = None,
+                spans: Results | None = None, cpu: bool = False):
+    """Fixed-length seeds: the S = `pieces` slots of every task hold the
+    intervals of S equal consecutive pieces of the read (the last takes the
+    remainder; a piece of no bases is an ignored slot), so that a near-copy of
+    an exactly matching read's locus becomes a candidate -- the greedy seed
+    search gives such a read one seed, the whole read.  Each piece is searched
+    as a batch of its own with kfmi_search / kfmi_search_strands (cpu=True: the
+    host searches) on the backend in effect; a REV task's pieces are those of
+    P', piece (start, len) of P' being the reverse strand of P[m - start - len
+    .. m - start).  Returns (intervals, spans), uint32 [ns * N, S, 2]; with
+    `intervals` and `spans` handles of S * ns * N entries on the device the
+    arrays are written to their host arrays and sent up (results_to_gpu)."""
+    reads = np.ascontiguousarray(reads, dtype=np.uint8)
+    n, m = reads.shape
+    s, ns = int(pieces), _strand_count(strands)
+    if s < 1 or s > 8:
+        raise KfmiError(33, "piece_seeds")
+    iv, sp = np.zeros((ns * n, s, 2), np.uint32), np.zeros((ns * n, s, 2), np.uint32)
+    if cpu:
+        find = lambda q, st: search_cpu_array(index, q, strands=st)   # noqa: E731
+    else:
+        find = lambda q, st: search_array(index, q, None, st)         # noqa: E731
+    for j, (start, ln) in enumerate(piece_bounds(m, s)):
+        if ln == 0 or n == 0:
+            continue
+        for strand in ((STRAND_FWD, STRAND_REV) if int(strands) == STRAND_BOTH else (int(strands),)):
+            rows = slice(strand - 1, None, 2) if ns == 2 else slice(None)
+            lo = start if strand == STRAND_FWD else m - start - ln
+            iv[rows, j] = find(np.ascontiguousarray(reads[:, lo:lo + ln]), strand).reshape(n, 2)
+            sp[rows, j] = (start, ln)
+    if intervals is not None:
+        intervals.array()[:] = iv.reshape(-1)
+        spans.array()[:] = sp.reshape(-1)
+        if not cpu:
+            results_to_gpu(intervals)
+            results_to_gpu(spans)
+    return iv, sp
+
+
 def map_reads_array(index: Index, reads: np.ndarray, backend: str | None = None, max_seeds: int = 4,
                     strands: int = STRAND_BOTH, max_occ: int = 8, max_mism: int | None = None, cpu: bool = False,
-                    text=None, band: int | None = None, max_edits: int | None = None):
+                    text=None, band: int | None = None, max_edits: int | None = None, mapq: bool = False,
+                    max_second: int | None = None, pieces: int | None = None):
     """Upload, seed search and verify of uint8 [N, m] reads in one call: where
     each task maps and with how many differences.  Returns (origin, mism, multi,
     scored), arrays of ns * N tasks (BOTH: task 2q + strand): origin -1 and
@@ -1231,16 +1335,24 @@ def map_reads_array(index: Index, reads: np.ndarray, backend: str | None = None,
     band=None scores candidates by their Hamming count (verify_seeds).  An
     integer band takes align_seeds instead: origin is then the begin position
     of the best banded placement, mism its edits, bounded by max_edits (None:
-    max_mism's value) -- reads with an indel of up to `band` bases map too."""
-    n, s = reads.shape[0], int(max_seeds)
+    max_mism's value) -- reads with an indel of up to `band` bases map too.
+    pieces=k takes piece_seeds' k fixed-length slots per task in place of the
+    greedy seeds (max_seeds is then k).  mapq=True needs a band and returns two
+    more arrays, (.., quality, gap): align_second and map_quality with
+    max_second (None: max_edits' value) after the align."""
+    n, s = reads.shape[0], int(max_seeds if pieces is None else pieces)
     ns = _strand_count(strands)
     mm = 0xFFFFFFFF if max_mism is None else int(max_mism)
     if band is not None and max_edits is not None:
         mm = int(max_edits)
+    if mapq and band is None:
+        raise ValueError("map_reads_array(mapq=True) needs a band")
+    m2 = mm if max_second is None else int(max_second)
     if backend and not cpu:
         set_backend(backend)
     q = Queries.from_array(reads)
     iv, sp, hits = Results.alloc(max(s, 0) * ns * n), Results.alloc(max(s, 0) * ns * n), Results.alloc(ns * n)
+    second, quals = (Results.alloc(ns * n), Results.alloc(ns * n)) if mapq else (None, None)
     tmp = None
     try:
         if cpu:
@@ -1250,29 +1362,47 @@ def map_reads_array(index: Index, reads: np.ndarray, backend: str | None = None,
             if rate != 1:
                 tmp = Index.build(bytes(text), k=1, d=64, sa_rate=1)
                 rate, sa = tmp.sa()
-            search_seeds_cpu(index, q, iv, sp, s, strands)
+            if pieces is None:
+                search_seeds_cpu(index, q, iv, sp, s, strands)
+            else:
+                piece_seeds(index, reads, s, strands, iv, sp, cpu=True)
             if band is None:
                 verify_seeds_cpu(text, sa, q, iv, sp, hits, s, strands, max_occ, mm)
             else:
                 align_seeds_cpu(text, sa, q, iv, sp, hits, s, strands, max_occ, band, mm)
+            if mapq:
+                align_second_cpu(text, sa, q, iv, sp, hits, second, s, strands, max_occ, band, m2)
+                map_quality_cpu(hits, second, quals, strands, m2)
         else:
             transfer_to_gpu(index, q, iv)
             transfer_to_gpu(index, None, sp)
             transfer_to_gpu(index, None, hits)
-            search_seeds(index, q, iv, sp, s, strands)
+            if pieces is None:
+                search_seeds(index, q, iv, sp, s, strands)
+            else:
+                piece_seeds(index, reads, s, strands, iv, sp)
             if band is None:
                 verify_seeds(index, q, iv, sp, hits, s, strands, max_occ, mm)
             else:
                 align_seeds(index, q, iv, sp, hits, s, strands, max_occ, band, mm)
+            if mapq:
+                transfer_to_gpu(index, None, second)
+                transfer_to_gpu(index, None, quals)
+                align_second(index, q, iv, sp, hits, second, s, strands, max_occ, band, m2)
+                map_quality(index, hits, second, quals, strands, m2)
+                transfer_to_cpu(quals)
             transfer_to_cpu(hits)
-        return decode_hits(hits.array().copy())
+        out = decode_hits(hits.array().copy())
+        if mapq:
+            ql = quals.array().copy().reshape(-1, 2).astype(np.int64)
+            out += (ql[:, 0], ql[:, 1])
+        return out
     finally:
         if tmp is not None:
             tmp.close()
-        q.close()
-        iv.close()
-        sp.close()
-        hits.close()
+        for h in (q, iv, sp, hits, second, quals):
+            if h is not None:
+                h.close()
 
 
 PATH_EDITS_MASK = 0x0000FFFF
