@@ -1020,7 +1020,8 @@ int32_t kfmi_set_path_chunk(uint64_t tasks);
  * backends, K = 3 / 4, device groups; KFMI_E_NOT_ON_DEVICE) and set
  * kfmi_last_timing to total, 0, their kernel.
  *   What the three calls do not do: reads of unequal length within a pair,
- * layouts other than forward-reverse, affine gaps, soft clipping, SAM output. */
+ * layouts other than forward-reverse, affine gaps, soft clipping, the pair
+ * fields of a SAM line (see "SAM lines"). */
 #define KFMI_WINDOW_MAX_LEN 4096u
 #define KFMI_PAIR_PROPER  0x00020000u   /* y bit 17: the record is one side of the pair's chosen combination */
 #define KFMI_PAIR_RESCUED 0x00040000u   /* y bit 18: that side is the record placed in the mate's window    */
@@ -1116,7 +1117,7 @@ int32_t kfmi_pair_hits_cpu(void *hits, void *rescued, void *paired, uint32_t rea
  * handles' host arrays.
  *   What neither call does: the quality of a pair (where the second-best
  * combination matters, not only the second-best side), affine gaps, soft
- * clipping, SAM text. */
+ * clipping. */
 #define KFMI_SECOND_TRUNCATED 0x00080000u   /* y bit 19: a slot held more rows than max_occ looked at        */
 #define KFMI_MAPQ_MAX         60u
 #define KFMI_MAPQ_PER_EDIT    10u
@@ -1131,6 +1132,120 @@ int32_t kfmi_align_second_cpu(const char *text, uint64_t n, const uint32_t *sa, 
 int32_t kfmi_map_quality(void *index, void *hits, void *second, void *quals,
                          uint32_t strands, uint32_t max_second);
 int32_t kfmi_map_quality_cpu(void *hits, void *second, void *quals, uint32_t strands, uint32_t max_second);
+
+/* ---- SAM lines (not in the reference, which stops at intervals) --------------
+ * The text form of a batch: one SAM record per read from the records the calls
+ * above leave on the device, with positions as a sequence name and a 1-based
+ * coordinate and with NM and MD, so that a consumer needs neither this library
+ * nor the text.
+ *
+ *   Contig table.  kfmi_contigs_create(names, begins, lengths, count, &contigs):
+ * `names` holds `count` NUL-terminated names back to back, contig i is the text
+ * positions [begins[i], begins[i] + lengths[i]).  KFMI_E_BAD_ARGUMENT, and
+ * nothing is created, for count = 0; a name that is empty, longer than 254
+ * bytes or holds a byte outside 33 .. 126; a length of 0; begins[i] +
+ * lengths[i] > begins[i + 1] (contigs ascend and do not overlap; gaps between
+ * them are allowed, because the `ref` loader leaves header bytes in the text)
+ * or a contig ending past 2^32 - 1.  The table's end is checked against the
+ * text's length by the call that uses it.  kfmi_sam_header(contigs, buf, cap)
+ * returns the bytes of "@HD\tVN:1.6\tSO:unknown\n" followed by one
+ * "@SQ\tSN:<name>\tLN:<length>\n" per contig and writes them to buf if cap
+ * holds them (no terminator); a negative error code for no table.  The device
+ * copy of the table is made by the first kfmi_sam_lines that uses it, on that
+ * index's device -- begins, lengths, the names as one byte array with a u32
+ * offset per contig -- and freed with the table; a table serves one device.
+ *
+ *   kfmi_sam_lines.  The handles, the strand modes and the task numbering are
+ * those of kfmi_align_paths: `hits`, `paths` and, where given, `quals` have ns *
+ * num entries, `cigars` ns * num * C with C = cigar_entries; `band` is the band
+ * the paths were made with.  Of `hits` only word x is read (the begin position
+ * B), of `paths` x (the end), D = y & KFMI_PATH_EDITS_MASK, the runs and
+ * KFMI_PATH_OVERFLOW, of `quals` only word x.  quals may be NULL.
+ *   Status of task t, n the text's length, m the read length, w = band.  The
+ * first of these that holds:
+ *     NONE      paths[t].x = KFMI_HIT_NONE.
+ *     OVERFLOW  paths[t].y carries KFMI_PATH_OVERFLOW.
+ *     SPAN      no contig i has begins[i] <= B and end <= begins[i] +
+ *               lengths[i]; or end <= B (a path of insertions only uses no
+ *               text base); or the placement does not lie in the window of its
+ *               band: n < m, B > n, B - c > w or end > c + m + w with c =
+ *               min(B, n - m) -- which a path made at another band may do, and
+ *               which covers end - B > m + 2w; or its runs are not between 1
+ *               and 2C runs of I, D, = or X, each of at least one base, whose
+ *               =, X and I lengths sum to m and whose =, X and D lengths sum
+ *               to end - B -- which no record of kfmi_align_paths does.
+ *     OK        otherwise; its contig is the i above, found by a binary search
+ *               over begins.
+ *   One line per read, in read order, each ending in "\n"; offsets[q] is where
+ * read q's line begins, offsets[num] the total.  With one strand the read's
+ * task is its only task.  In BOTH mode it is chosen among the read's OK tasks:
+ * the one with fewer path edits D, the FWD task on a tie.
+ *   A mapped line (the read's task is OK), fields separated by one tab:
+ *     QNAME FLAG RNAME POS MAPQ CIGAR * 0 0 SEQ * NM:i:<D> MD:Z:<md>
+ *   QNAME: name_base + q in decimal.  FLAG: 0, or 16 for a REV task.  RNAME:
+ * the contig's name.  POS: B - begins[i] + 1.  MAPQ: min(quals[t].x, 254), 255
+ * when quals is NULL.  CIGAR: the task's runs in order as <len><op> with the
+ * character "MIDNSHP=X"[op]; under KFMI_SAM_CIGAR_M every maximal sequence of
+ * adjacent = and X runs is one M run of the summed length.  SEQ: "ACGT"[code]
+ * of the task's code words in the order they were aligned, which for a REV
+ * task is the reverse complement, as SAM wants it beside flag 16.  MD: with a
+ * counter c = 0, over the runs: = adds its length to c; I does nothing; X
+ * writes, per base, c in decimal and the text's letter at that position, then
+ * c = 0; D writes c, "^" and the run's text letters, then c = 0; at the end c
+ * is written.  Runs 3= 1X 1D 4= give "3A0^C4", a leading X "0A..", two adjacent
+ * mismatches "..A0C..".  Text letters are "ACGT"[code] of the 2-bit text.
+ *   An unmapped line (no OK task):
+ *     QNAME 4 * 0 0 * * 0 0 SEQ * YU:i:<r>
+ * with SEQ the read as given (the FWD form) and r the largest status code
+ * among the read's tasks, NONE = 0, OVERFLOW = 1, SPAN = 2.
+ *   Nothing depends on the evaluation order; kfmi_sam_lines_cpu writes the
+ * same bytes from the handles' host arrays and the ASCII text (OpenMP over
+ * reads, a length pass, a prefix sum, a write pass; no index, no device).
+ *   Limits.  SEQ is in the mapped alphabet: base2index of the read's bytes, so
+ * a read's N appears as G, consistently with the = and X of its CIGAR; read
+ * names and the original letters are not kept.  No base qualities (QUAL is
+ * "*").  No pair fields: RNEXT, PNEXT and TLEN are "*", 0, 0 and flags 1, 2,
+ * 32, 64 and 128 are never set, whatever kfmi_pair_hits chose.  A placement
+ * that crosses a contig's edge is unmapped (SPAN), not clipped.  No BAM.
+ *   Arguments, coverage, refusals.  Coverage and the tables built on demand are
+ * those of kfmi_align_paths; `hits`, `paths`, `cigars` and `quals` are distinct
+ * handles on the index's device.  KFMI_E_BAD_ARGUMENT: what kfmi_align_paths
+ * refuses, an option bit other than KFMI_SAM_CIGAR_M, name_base + num
+ * overflowing 64 bits, a table whose last contig ends past n, a table whose
+ * device copy is on another device, sam = NULL.  A refused call writes nothing
+ * and leaves *sam untouched.
+ *   The handle.  kfmi_sam_num: the lines; kfmi_sam_bytes: their bytes;
+ * kfmi_sam_offsets: num + 1 host values; kfmi_sam_text: the bytes on the host
+ * (no terminator), copied from the device at the first call, NULL when that
+ * fails; kfmi_sam_free frees host and device memory and clears the pointer.
+ *   The device side is two kernels around a scan: a length pass on records
+ * alone, an exclusive scan of the lengths (u32 -> u64), and a write pass with
+ * the read in registers that formats a wave's lines into a 16 KB tile of LDS
+ * and copies the tile out with 16-byte stores.
+ * kfmi_set_sam_form(1) is a process-wide test knob that makes every lane write
+ * its line straight to device memory instead; 0 = the tile.  No byte depends on
+ * it.  kfmi_last_timing: total, 0, the sum of both passes and the scan (ms,
+ * device time; the allocation of the text between them is not in it);
+ * kfmi_sam_last_passes gives the calling thread's last call apart: the length
+ * pass, the scan, the write pass. */
+#define KFMI_SAM_CIGAR_M 1u   /* options bit 0: adjacent = and X runs merge into one M run */
+int32_t kfmi_contigs_create(const char *names, const uint32_t *begins, const uint32_t *lengths,
+                            uint32_t count, void **contigs);
+int32_t kfmi_contigs_free(void **contigs);
+int64_t kfmi_sam_header(void *contigs, char *buf, uint64_t cap);
+int32_t kfmi_sam_lines(void *index, void *queries, void *contigs, void *hits, void *paths, void *cigars,
+                       void *quals, uint32_t strands, uint32_t cigar_entries, uint32_t band,
+                       uint32_t options, uint64_t name_base, void **sam);
+int32_t kfmi_sam_lines_cpu(const char *text, uint64_t n, void *queries, void *contigs, void *hits, void *paths,
+                           void *cigars, void *quals, uint32_t strands, uint32_t cigar_entries, uint32_t band,
+                           uint32_t options, uint64_t name_base, int32_t nthreads, void **sam);
+uint64_t        kfmi_sam_num(void *sam);
+uint64_t        kfmi_sam_bytes(void *sam);
+const uint64_t *kfmi_sam_offsets(void *sam);
+const char     *kfmi_sam_text(void *sam);
+int32_t         kfmi_sam_free(void **sam);
+int32_t         kfmi_set_sam_form(uint32_t form);
+int32_t         kfmi_sam_last_passes(double *ms_length, double *ms_scan, double *ms_write);
 
 /* ---- walk trace (tests and diagnosis; not in the reference, not timed) -------
  * The fused forward task kernel ends a walk early through three shortcuts --

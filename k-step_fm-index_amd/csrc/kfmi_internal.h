@@ -96,6 +96,30 @@ typedef struct {
   char    *h_reference;
 } kfmi_ref_t;
 
+/* sam.c: the contig table and the SAM text of a batch.  Both are made on the host; the HIP layer (kfmi_sam.hip) hangs
+ * its device memory on them with the function that frees it, so that sam.c needs no device. */
+typedef struct {
+  uint32_t  count;
+  uint32_t *begins, *lengths, *name_off;   /* count, count, count + 1: name i is names[name_off[i] .. name_off[i + 1]) */
+  char     *names;
+  pthread_mutex_t mu;                      /* guards the device copy's making */
+  void     *d_mem;                         /* [begins | lengths | name_off | names], NULL until a device call uses it */
+  int32_t   d_device;
+  void    (*d_free)(void *d_mem, int32_t device);
+} kfmi_contigs_t;
+
+typedef struct {
+  uint64_t  num, bytes;
+  uint64_t *h_off;                         /* num + 1 */
+  char     *h_text;                        /* bytes; NULL until kfmi_sam_text where the text is on a device */
+  pthread_mutex_t mu;                      /* guards the first kfmi_sam_text */
+  void     *d_text;
+  int32_t   d_device;
+  int32_t (*d_fetch)(const void *d_text, int32_t device, char *dst, uint64_t bytes);
+  void    (*d_free)(void *d_text, int32_t device);
+} kfmi_sam_t;
+kfmi_sam_t *kfmi_sam_alloc(uint64_t num);   /* h_off allocated and zeroed; NULL when out of memory */
+
 /* verify.c: what kfmi_verify_seeds_cpu and kfmi_align_seeds_cpu share -- the
  * argument checks, the reverse complements of REV / BOTH and the OpenMP loop
  * over the tasks; `task` forms one task's record from its m bases and S slots */

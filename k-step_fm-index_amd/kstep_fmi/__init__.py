@@ -189,6 +189,18 @@ def load() -> ctypes.CDLL:
         "kfmi_align_second_cpu": (i32, [vp, u64, vp, u64, vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, i32]),
         "kfmi_map_quality": (i32, [vp, vp, vp, vp, u32, u32]),
         "kfmi_map_quality_cpu": (i32, [vp, vp, vp, u32, u32]),
+        "kfmi_contigs_create": (i32, [vp, vp, vp, u32, pvp]),
+        "kfmi_contigs_free": (i32, [pvp]),
+        "kfmi_sam_header": (ctypes.c_int64, [vp, vp, u64]),
+        "kfmi_sam_lines": (i32, [vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, u64, pvp]),
+        "kfmi_sam_lines_cpu": (i32, [vp, u64, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, u64, i32, pvp]),
+        "kfmi_sam_num": (u64, [vp]),
+        "kfmi_sam_bytes": (u64, [vp]),
+        "kfmi_sam_offsets": (vp, [vp]),
+        "kfmi_sam_text": (vp, [vp]),
+        "kfmi_sam_free": (i32, [pvp]),
+        "kfmi_set_sam_form": (i32, [u32]),
+        "kfmi_sam_last_passes": (i32, [ctypes.POINTER(ctypes.c_double)] * 3),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -1499,6 +1511,193 @@ def map_paths_array(index: Index, reads: np.ndarray, backend: str | None = None,
     finally:
         for h in (q, iv, sp, hits, paths, cig):
             h.close()
+
+
+SAM_CIGAR_M = 1
+SAM_NONE, SAM_OVERFLOW, SAM_SPAN = 0, 1, 2
+
+
+class Contigs(_Handle):
+    """kfmi_contigs_create: the sequences of a concatenated text, contig i the
+    text positions [begins[i], begins[i] + lengths[i]) under names[i]."""
+    _free = "kfmi_contigs_free"
+
+    @classmethod
+    def create(cls, names, begins, lengths) -> "Contigs":
+        raw = b"".join((n if isinstance(n, bytes) else str(n).encode()) + b"\0" for n in names)
+        b = np.ascontiguousarray(begins, dtype=np.uint32)
+        ln = np.ascontiguousarray(lengths, dtype=np.uint32)
+        if b.size != len(names) or ln.size != len(names):
+            raise KfmiError(33, "kfmi_contigs_create")
+        out = ctypes.c_void_p()
+        _check(load().kfmi_contigs_create(ctypes.c_char_p(raw), b.ctypes.data_as(ctypes.c_void_p),
+                                          ln.ctypes.data_as(ctypes.c_void_p), len(names), ctypes.byref(out)),
+               "kfmi_contigs_create")
+        return cls(out.value)
+
+    def header(self) -> bytes:
+        """kfmi_sam_header: "@HD" and one "@SQ" line per contig."""
+        need = load().kfmi_sam_header(self.ptr, None, 0)
+        if need < 0:
+            raise KfmiError(-need, "kfmi_sam_header")
+        buf = ctypes.create_string_buffer(int(need) + 1)
+        load().kfmi_sam_header(self.ptr, buf, need)
+        return buf.raw[:need]
+
+
+def fasta_contigs(data: bytes):
+    """(text, Contigs) of a multi-record FASTA: the records' sequence bytes
+    concatenated with no separator under the `map` alphabet's byte mapping
+    ("ACGT"[base2index(byte)]: lowercase -> uppercase, N -> G), each record a
+    contig named by its header line up to the first whitespace."""
+    code = np.arange(256, dtype=np.uint32)
+    f2, b1 = code & 2, code & 4
+    lut = np.frombuffer(b"ACGT", dtype=np.uint8)[(b1 | np.where(b1 != 0, f2 ^ 2, f2)) >> 1]
+    names, begins, lengths, parts, pos = [], [], [], [], 0
+    for line in bytes(data).splitlines():
+        line = line.strip()
+        if line.startswith(b">"):
+            head = line[1:].split()
+            names.append(head[0] if head else b"")
+            begins.append(pos)
+            lengths.append(0)
+        elif line:
+            if not names:
+                raise ValueError("fasta_contigs: sequence before the first '>' line")
+            parts.append(lut[np.frombuffer(line, dtype=np.uint8)])
+            lengths[-1] += len(line)
+            pos += len(line)
+    text = np.concatenate(parts).tobytes() if parts else b""
+    return text, Contigs.create(names, begins, lengths)
+
+
+class Sam(_Handle):
+    """A batch's SAM lines (kfmi_sam_lines / kfmi_sam_lines_cpu): one per read."""
+    _free = "kfmi_sam_free"
+
+    @property
+    def num(self) -> int:
+        return int(load().kfmi_sam_num(self.ptr))
+
+    @property
+    def nbytes(self) -> int:
+        return int(load().kfmi_sam_bytes(self.ptr))
+
+    def offsets(self) -> np.ndarray:
+        """uint64 [num + 1]: where each read's line begins, and the total."""
+        return _owned_view(load().kfmi_sam_offsets(self.ptr), 8 * (self.num + 1), np.uint64, self).copy()
+
+    def text(self) -> bytes:
+        """The lines' bytes; copied from the device at the first call."""
+        addr = load().kfmi_sam_text(self.ptr)
+        if not addr:
+            raise KfmiError(32, "kfmi_sam_text")
+        return ctypes.string_at(addr, self.nbytes)
+
+    def lines(self) -> list:
+        """One bytes object per read, without the newline."""
+        t, off = self.text(), self.offsets()
+        return [t[int(off[i]):int(off[i + 1]) - 1] for i in range(self.num)]
+
+
+def sam_lines(index: Index, queries: Queries, contigs: Contigs, hits: Results, paths: Results, cigars: Results,
+              quals: Results | None, strands: int, cigar_entries: int, band: int, options: int = 0,
+              name_base: int = 0) -> Sam:
+    """kfmi_sam_lines: one SAM line per read from the records align_seeds,
+    align_paths (at `band`) and map_quality (or None: MAPQ 255) left on the
+    device; QNAME is name_base + the read's number.  SAM_CIGAR_M in `options`
+    merges adjacent = and X runs into M."""
+    out = ctypes.c_void_p()
+    _check(load().kfmi_sam_lines(index.ptr, queries.ptr, contigs.ptr, hits.ptr, paths.ptr, cigars.ptr,
+                                 quals.ptr if quals is not None else None, int(strands), int(cigar_entries),
+                                 int(band), int(options), int(name_base), ctypes.byref(out)), "kfmi_sam_lines")
+    return Sam(out.value)
+
+
+def sam_lines_cpu(text, queries: Queries, contigs: Contigs, hits: Results, paths: Results, cigars: Results,
+                  quals: Results | None, strands: int, cigar_entries: int, band: int, options: int = 0,
+                  name_base: int = 0, nthreads: int = 0) -> Sam:
+    """kfmi_sam_lines_cpu: the same bytes on the host, from the text (bytes or
+    uint8 array of n bases) and the handles' host arrays."""
+    t = np.ascontiguousarray(np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text,
+                             dtype=np.uint8)
+    out = ctypes.c_void_p()
+    _check(load().kfmi_sam_lines_cpu(t.ctypes.data_as(ctypes.c_void_p), t.size, queries.ptr, contigs.ptr, hits.ptr,
+                                     paths.ptr, cigars.ptr, quals.ptr if quals is not None else None, int(strands),
+                                     int(cigar_entries), int(band), int(options), int(name_base), int(nthreads),
+                                     ctypes.byref(out)), "kfmi_sam_lines_cpu")
+    return Sam(out.value)
+
+
+def set_sam_form(form: int) -> None:
+    """kfmi_set_sam_form (process-wide test knob): 0 = a wave's lines go through
+    its LDS tile, 1 = every lane writes its line straight to device memory."""
+    _check(load().kfmi_set_sam_form(int(form)), "kfmi_set_sam_form")
+
+
+def sam_last_passes():
+    """(length pass, scan, write pass) of the calling thread's last sam_lines, ms."""
+    a, b, c = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+    load().kfmi_sam_last_passes(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c))
+    return a.value, b.value, c.value
+
+
+def map_sam_array(index: Index, reads: np.ndarray, contigs: Contigs, backend: str | None = None, max_seeds: int = 4,
+                  strands: int = STRAND_BOTH, max_occ: int = 8, band: int = 3, max_edits: int | None = None,
+                  cigar_entries: int = 8, mapq: bool = False, max_second: int | None = None, options: int = 0,
+                  name_base: int = 0, cpu: bool = False, text=None) -> bytes:
+    """Upload, seed search, align_seeds, (align_second and map_quality when
+    mapq), align_paths and sam_lines of uint8 [N, m] reads in one call: the
+    header and one line per read, as bytes.  cpu=True chains the host forms
+    instead and needs `text`, the indexed text (see map_reads_array)."""
+    n, s = reads.shape[0], int(max_seeds)
+    ns = _strand_count(strands)
+    me = 0xFFFFFFFF if max_edits is None else int(max_edits)
+    m2 = me if max_second is None else int(max_second)
+    c = int(cigar_entries)
+    if backend and not cpu:
+        set_backend(backend)
+    q = Queries.from_array(reads)
+    iv, sp = Results.alloc(max(s, 0) * ns * n), Results.alloc(max(s, 0) * ns * n)
+    hits, paths, cig = Results.alloc(ns * n), Results.alloc(ns * n), Results.alloc(max(c, 0) * ns * n)
+    second, quals = (Results.alloc(ns * n), Results.alloc(ns * n)) if mapq else (None, None)
+    tmp = sam = None
+    try:
+        if cpu:
+            if text is None:
+                raise ValueError("map_sam_array(cpu=True) needs the indexed text")
+            rate, sa = index.sa()
+            if rate != 1:
+                tmp = Index.build(bytes(text), k=1, d=64, sa_rate=1)
+                rate, sa = tmp.sa()
+            search_seeds_cpu(index, q, iv, sp, s, strands)
+            align_seeds_cpu(text, sa, q, iv, sp, hits, s, strands, max_occ, band, me)
+            if mapq:
+                align_second_cpu(text, sa, q, iv, sp, hits, second, s, strands, max_occ, band, m2)
+                map_quality_cpu(hits, second, quals, strands, m2)
+            align_paths_cpu(text, q, hits, paths, cig, strands, band, me, c)
+            sam = sam_lines_cpu(text, q, contigs, hits, paths, cig, quals, strands, c, band, options, name_base)
+        else:
+            transfer_to_gpu(index, q, iv)
+            for h in (sp, hits, paths, cig, second, quals):
+                if h is not None:
+                    transfer_to_gpu(index, None, h)
+            search_seeds(index, q, iv, sp, s, strands)
+            align_seeds(index, q, iv, sp, hits, s, strands, max_occ, band, me)
+            if mapq:
+                align_second(index, q, iv, sp, hits, second, s, strands, max_occ, band, m2)
+                map_quality(index, hits, second, quals, strands, m2)
+            align_paths(index, q, hits, paths, cig, strands, band, me, c)
+            sam = sam_lines(index, q, contigs, hits, paths, cig, quals, strands, c, band, options, name_base)
+        return contigs.header() + sam.text()
+    finally:
+        if sam is not None:
+            sam.close()
+        if tmp is not None:
+            tmp.close()
+        for h in (q, iv, sp, hits, paths, cig, second, quals):
+            if h is not None:
+                h.close()
 
 
 WINDOW_MAX_LEN = 4096
